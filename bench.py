@@ -14,6 +14,21 @@ HBM before timing.
   python bench.py [--gpus N] [--steps K] [--warmup W] [--kernel bit|byte]
                   [--scaling weak|strong] [--size 65536]
                   [--workload random|p46gun_big] [--partition auto|cart|rows|cols]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline rate needs and nothing else: set-up,
+warm-up, the --steps timed generations, the result line (metric, value,
+ms_per_step, the configuration, and the roofline / call objects where the
+timed call's own events carry them: one shard on one stream).  --full adds
+everything that takes GPU or CPU runs of its own: the stream-copy ceiling
+(roofline.hbm.copy_ceiling_GBps), the K statistics generations behind the
+"phases" and roofline objects of multi-stream lines (N > 1, --loopback),
+"parity_vs_1gpu" and "cpu_baseline".
+
+--dump-outputs DIR writes, after the timed call, the grid that call left (what
+Life.gather_bits() hands a caller) as float .npy files, see dump_outputs().
+The inputs depend only on the arguments (--seed), so two builds run with the
+same arguments can be compared file by file.
 
 Partition (life_dims_choose): "cart" (the default for both scalings) is
 6-cartesian's MPI_Dims_create {2,1} / {2,2} / {4,2} split of life_cart.c:117-124
@@ -36,8 +51,8 @@ the line says n_gpus = the devices actually used, config.shards = N.  Every
 line carries config.devices (distinct PCI bus ids over all ranks) and
 config.rccl_nranks (ncclCommCount).
 `--shape WxH` replaces --size^2 (the per-GPU blocks of configs[3]).
-Every N > 1 line ends with "phases" (mean ring / interior / halo / block
-times per exchange, from HIP events on the three streams) and
+With --full every N > 1 line ends with "phases" (mean ring / interior / halo /
+block times per exchange, from HIP events on the three streams) and
 "parity_vs_1gpu" (the N-shard grid against the same grid run as one shard).
 """
 from __future__ import annotations
@@ -89,12 +104,20 @@ def parse():
                    help="shard shape (life_dims_choose); default: cart (MPI_Dims_create, life_cart.c:117-118: "
                         "configs[3]'s and configs[4]'s 2-D split); auto = row strips when each is >= 1024 rows tall")
     p.add_argument("--seed", type=int, default=1)
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="cpu_baseline sample budget (seconds of CPU work)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check what the headline rate does not need: the stream-copy ceiling, the "
+                        "statistics generations of multi-stream lines (phases, roofline), parity_vs_1gpu (N > 1) "
+                        "and cpu_baseline (N = 1)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed call, write the grid it left to DIR/<name>.npy (float32 / float64, a seeded "
+                        "row sample where the grid is large; see dump_outputs)")
+    p.add_argument("--cpu-seconds", type=float, default=12.0,
+                   help="--full: cpu_baseline sample budget (seconds of CPU work)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     p.add_argument("--parity-seconds", type=float, default=60.0,
-                   help="N > 1: the 1-GPU reference re-runs the timed generations when that is estimated to take "
-                        "less than this, else a fresh 3K+1-generation run of both")
-    p.add_argument("--no-parity", action="store_true")
+                   help="--full, N > 1: the 1-GPU reference re-runs the timed generations when that is estimated to "
+                        "take less than this, else a fresh 3K+1-generation run of both")
+    p.add_argument("--no-parity", action="store_true", help="--full without the parity_vs_1gpu leg")
     p.add_argument("--rank-mode", action="store_true",
                    help="one-process-per-GPU set-up (gloo bootstrap, RCCL communicator) even at world 1")
     p.add_argument("--flow", type=int, default=None, choices=[0, 1, 2, 3],
@@ -234,6 +257,51 @@ def parity_vs_1gpu(a, life, grid, nx, ny, gens_done, elapsed, n_gpus, rank, dist
         return None
     return {"ok": got == want, "generations": gens, "same_run": same_run, "checksum": got[0], "live": got[1],
             "reference": {"checksum": want[0], "live": want[1], "shards": 1, "device": 0}}
+
+
+DUMP_CELL_BYTES = 32 << 20  # cells.npy at most; the other files are 8 bytes per row and less
+DUMP_SEED = 20240229  # of the row sample (a constant: the same rows whatever --seed)
+
+
+def dump_outputs(life, dirpath, rank_mode, rank, world):
+    """--dump-outputs: the grid the timed call left, as a caller receives it
+    (Life.gather_bits(): the collect packed on the device), written by the
+    gather's root (the last rank in rank mode, as life_collect) to DIR:
+
+      cells.npy           float32 (rows, nx), 0.0 / 1.0: every row where that is
+                          at most 32 MiB, else a fixed, seeded sample of rows
+      cells_rows.npy      float64 (rows,): the grid row of each row of cells.npy
+      row_population.npy  float64 (ny,): live cells of every grid row
+      live_count.npy      float64 (): Life.live_count()
+      checksum.npy        float64 (2,): Life.checksum(), high and low 32 bits
+
+    so the sample compares cell for cell and the other three cover the whole
+    grid.  Collective in rank mode (census all-reduce, gather)."""
+    import ctypes
+
+    import numpy as np
+
+    live, census = life.live_count(), life.checksum()
+    if rank_mode and rank != world - 1:
+        lm._check(lm._lib().life_dev_gather_bits(life._h, ctypes.POINTER(ctypes.c_uint8)()), "gather_bits")
+        return
+    bits = life.gather_bits()
+    ny, nx = life.ny, life.nx
+    if nx % 8:  # the unused high bits of a row's last byte
+        bits[:, -1] &= (1 << (nx % 8)) - 1
+    nrows = min(ny, max(1, DUMP_CELL_BYTES // (4 * nx)))
+    rows = np.arange(ny) if nrows == ny else np.sort(np.random.default_rng(DUMP_SEED).choice(ny, nrows, replace=False))
+    cells = np.unpackbits(bits[rows], axis=1, count=nx, bitorder="little").astype(np.float32)
+    popcount = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)
+    row_population = np.empty(ny, dtype=np.float64)
+    chunk = max(1, (64 << 20) // bits.shape[1])
+    for y in range(0, ny, chunk):
+        row_population[y:y + chunk] = popcount[bits[y:y + chunk]].sum(axis=1, dtype=np.int64)
+    os.makedirs(dirpath, exist_ok=True)
+    for name, arr in (("cells", cells), ("cells_rows", rows.astype(np.float64)), ("row_population", row_population),
+                      ("live_count", np.float64(live)),
+                      ("checksum", np.array([census >> 32, census & 0xFFFFFFFF], dtype=np.float64))):
+        np.save(os.path.join(dirpath, name + ".npy"), arr)
 
 
 def shape_of(a):
@@ -387,9 +455,12 @@ def main():
     # passes 0.494-0.501 ms in the call, 0.454-0.457 ms in the statistics run),
     # so the phases understated the call's own blocks.
     # LIFE_BENCH_PHASES_TIMED=1 (or no warmup): all of it inside the timed call.
+    # Those K generations are a run of their own, so only --full takes them:
+    # a plain multi-stream line has neither object.
     phases_timed = os.environ.get("LIFE_BENCH_PHASES_TIMED", "0") == "1" or a.warmup <= 0
     multi = n_gpus > 1 or a.loopback
-    stats_after = multi and not phases_timed
+    stats_after = multi and not phases_timed and a.full
+    have_stats = not multi or phases_timed or a.full
     life.set_timing(True)
     life.step(a.warmup)
     life.sync()
@@ -427,35 +498,44 @@ def main():
     elapsed, host_enq, pass_enq, span = allmax([elapsed, call["host_enqueue_ms"], call["pass_enqueue_max_ms"],
                                                 call["device_span_ms"]])
     K = life.layout().generations_per_exchange
+    ph = None
+
+    def read_stats():
+        return (*life.kernel_stats(), *life.kernel_work(), life.phase_stats() if multi else None)
+
+    if have_stats and not stats_after:  # the timed call's own events, before anything else launches
+        avg_ms, launches, bytes_per_launch, updates_per_launch, valu_per_launch, ph = read_stats()
+    if a.dump_outputs:
+        # the grid as the timed call left it: before the statistics
+        # generations (which then start from a GPU the gather has idled)
+        dump_outputs(life, a.dump_outputs, rank_mode, rank, world)
     if stats_after:
         life.set_timing(True)
         life.step(K)
         life.sync()
-        ph = life.phase_stats()
-    avg_ms, launches, bytes_per_launch = life.kernel_stats()
-    updates_per_launch, valu_per_launch = life.kernel_work()
-    if phases_timed:
-        ph = life.phase_stats()
+        avg_ms, launches, bytes_per_launch, updates_per_launch, valu_per_launch, ph = read_stats()
     live = life.live_count()
     lay = life.layout()
     temporal = lay.generations_per_exchange > 1
 
     # a measured stream-copy ceiling next to the spec peak
     # (rank 0's GPU, after the timed region; 2 x 2 GiB buffers)
-    copy_gbps = lm.measure_copy(local_rank, 2 << 30, 5) if rank == 0 else 0.0
+    copy_gbps = lm.measure_copy(local_rank, 2 << 30, 5) if (a.full and rank == 0) else 0.0
 
     parity = None
-    if n_gpus > 1 and not a.no_parity:
+    if a.full and n_gpus > 1 and not a.no_parity:
         # the grid has advanced warmup + steps (+ K statistics generations)
         parity = parity_vs_1gpu(a, life, grid, nx, ny, a.warmup + a.steps + (K if stats_after else 0), elapsed,
                                 n_gpus, rank, dist, barrier_sync)
-    if multi:
+    if ph is not None:
         exposed = allmax([ph["block_ms"] - ph["interior_ms"], ph["block_ms"], ph["halo_ms"]])
 
     if rank == 0:
         cells = float(nx) * float(ny) * a.steps
         bpu = 0.25 if a.kernel == "bit" else 2.0  # algorithmic HBM bytes per cell-update
         value = cells / elapsed / 1e9
+        if not have_stats:  # a plain multi-stream line: no launch statistics, no roofline object below
+            avg_ms, launches, bytes_per_launch, updates_per_launch, valu_per_launch = 0.0, 0, 0.0, 0.0, 0.0
         hbm = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
         gens_per_launch = updates_per_launch / (bytes_per_launch / bpu) if bytes_per_launch > 0 else 0.0
         variant = a.kernel + ("_temporal" if temporal else "_onegen")
@@ -469,7 +549,7 @@ def main():
         hbm_obj = {"achieved": round(hbm, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                    "frac": round(hbm / HBM_PEAK_GBS, 4),
                    "bytes_per_launch": bytes_per_launch,
-                   "copy_ceiling_GBps": round(copy_gbps, 1),
+                   "copy_ceiling_GBps": round(copy_gbps, 1) if a.full else None,  # a run of its own: --full
                    "frac_of_copy_ceiling": round(hbm / copy_gbps, 4) if copy_gbps > 0 else None,
                    # SURVEY 8(d)'s per-update figure (0.25 B bit / 2 B byte) x the
                    # cell-updates of a launch: above the HBM peak once a launch
@@ -551,7 +631,9 @@ def main():
                      "device_span_ms": round(span, 4),
                      "outside_span_ms": round(elapsed * 1e3 - span, 4) if span > 0 else None},
         }
-        if n_gpus > 1 or a.loopback:
+        if not have_stats:
+            del out["roofline"]
+        if ph is not None:
             out["phases"] = {"ring_ms": round(ph["ring_ms"], 4), "interior_ms": round(ph["interior_ms"], 4),
                              "halo_ms": round(ph["halo_ms"], 4), "block_ms": round(ph["block_ms"], 4),
                              "blocks": ph["blocks"], "exposed_ms": round(ph["block_ms"] - ph["interior_ms"], 4),
@@ -564,7 +646,7 @@ def main():
                                         "phase events)")}
         if parity is not None:
             out["parity_vs_1gpu"] = parity
-        if n_gpus == 1 and not a.no_cpu_baseline:
+        if a.full and n_gpus == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.cpu_seconds)
         print(json.dumps(out), flush=True)
     life.close()

@@ -3,7 +3,8 @@
 from controlled single-GPU measurements.
 
 Every per-GPU block is rehearsed on one MI355X as an RCCL-loopback line
-(`bench.py --rank-mode --loopback --loopback-axes A --shape WxH`: the block a
+(`bench.py --full --rank-mode --loopback --loopback-axes A --shape WxH`, --full
+for the "phases" object: the block a
 periodic partition of itself, its halos through RCCL, the ring / interior /
 halo schedule of the multi-GPU path), exchanging only the axes its N
 partitions (MPI_Dims_create: N = 2 -> {2,1}, x only; N = 4 -> {2,2} and N = 8

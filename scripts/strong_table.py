@@ -2,8 +2,8 @@
 """Predicted strong-scaling efficiency of configs[3] (65536^2 split over
 N = 2/4/8 GPUs, MPI_Dims_create blocks {2,1} / {2,2} / {4,2}) from
 single-GPU measurements: each GPU's block is rehearsed on
-one MI355X as an RCCL loopback line (`bench.py --rank-mode --loopback --shape
-WxH`: the block a periodic partition of itself, its halos through RCCL, the
+one MI355X as an RCCL loopback line (`bench.py --full --rank-mode --loopback --shape
+WxH`, --full for the "phases" object: the block a periodic partition of itself, its halos through RCCL, the
 ring / interior / halo schedule of the multi-GPU path), and
 
     predicted efficiency(N) = rate(block_N) / rate(65536^2, 1 GPU)
