@@ -211,6 +211,43 @@ int64_t life_dev_live_count(life_dev *d);
  * compared at sizes no host gather reaches.  Blocking. */
 int life_dev_checksum(life_dev *d, uint64_t *sum);
 
+/* ---- Sparse I/O for grids no host buffer holds (no reference counterpart:
+ * life_init fills a full host grid, life_cart.c:104-109, and life_collect
+ * gathers one, :281-305).  Each shard works on its own block on the device;
+ * nothing of size nx*ny is allocated on the host or crosses PCIe.  All four
+ * calls are blocking and valid at any step boundary.  In rank mode they are
+ * COLLECTIVE: every rank passes the same arguments, and the two readers give
+ * every rank the whole result -- each rank adds its pieces to a zeroed device
+ * buffer and the buffers are summed with ncclAllReduce, as the census is.
+ * With world > 1 that combine has never executed (one-GPU box), as the
+ * gather fan-in above has not; world 1 with a unique id runs it on a
+ * one-rank communicator. */
+
+/* Every cell dead: the state after life_dev_upload of an all-zero grid. */
+int life_dev_clear(life_dev *d);
+
+/* The n cells (xy[2k], xy[2k+1]) = (x, y), x on the contiguous axis, become
+ * alive (alive != 0) or dead (0); every other cell is untouched.  Coordinates
+ * wrap with a true modulo (any int64; as the driver's .cfg loader);
+ * duplicates are allowed.  The list is staged on each shard's device, a
+ * kernel keeps the cells of the shard's block, and the halos are then
+ * refilled as after an upload (a part-used deep halo included).  n == 0 is a
+ * no-op; n < 0, or xy == NULL with n > 0, is LIFE_EINVAL. */
+int life_dev_set_cells(life_dev *d, const int64_t *xy, int64_t n, int alive);
+
+/* The periodic window of w x h cells at (x0, y0): cells[j*w + i] (0/1) is
+ * cell ((x0 + i) mod nx, (y0 + j) mod ny); x0, y0 any int64, 1 <= w <= nx,
+ * 1 <= h <= ny (else LIFE_EINVAL).  Read straight from the padded blocks (up
+ * to four wrapped pieces per shard); device staging is w*h bytes. */
+int life_dev_gather_rect(life_dev *d, int64_t x0, int64_t y0, int64_t w, int64_t h, uint8_t *cells);
+
+/* Block-summed density map: ceil(ny/fy) rows of ceil(nx/fx) counts,
+ * counts[by*bw + bx] = live cells with x / fx == bx and y / fy == by (the last
+ * bin row / column may be partial).  fx, fy >= 1 and fx*fy < 2^32, else
+ * LIFE_EINVAL; a factor larger than the grid gives one bin on that axis.
+ * One streaming pass over the owned words (popcounts under per-bin masks). */
+int life_dev_gather_density(life_dev *d, int64_t fx, int64_t fy, uint32_t *counts);
+
 int life_dev_sync(life_dev *d);
 /* life_dev_sync, then (rank mode) an all-reduce every rank joins: the
  * synchronisation the reference gets from its blocking MPI calls; the driver

@@ -1751,6 +1751,142 @@ int life_dev_checksum(life_dev *d, uint64_t *sum) {
     return LIFE_OK;
 }
 
+// ---- sparse I/O: nothing of size nx*ny on the host or over PCIe ----
+
+int life_dev_clear(life_dev *d) {
+    if (!d) return LIFE_EINVAL;
+    CHK(life_dev_sync(d));  // behind the work on all three streams
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        HIPCHK(hipMemsetAsync(s.buf[s.cur], 0, (size_t)(s.lay.pitch * s.lay.rows), s.stream));
+    }
+    CHK(exchange(d, 0, false));  // as life_dev_upload: the deep-halo count restarts
+    return life_dev_sync(d);
+}
+
+int life_dev_set_cells(life_dev *d, const int64_t *xy, int64_t n, int alive) {
+    if (!d || n < 0 || (n > 0 && !xy)) return LIFE_EINVAL;
+    if (n == 0) return LIFE_OK;
+    CHK(life_dev_sync(d));  // the edit orders behind the work on all three streams
+    constexpr int64_t kChunk = 1 << 20;  // pairs staged at a time (16 MiB)
+    for (int64_t i = 0; i < n; i += kChunk) {
+        const int64_t m = std::min(kChunk, n - i);
+        for (Shard &s : d->shards) {
+            HIPCHK(hipSetDevice(s.device));
+            uint8_t *stage;
+            CHK(stage_buffer(s, (size_t)m * 2 * sizeof(int64_t), &stage));
+            // `xy` is the caller's pageable memory: ordered on the shard's
+            // stream and waited for (see life_dev_upload)
+            HIPCHK(hipMemcpyAsync(stage, xy + 2 * i, (size_t)m * 2 * sizeof(int64_t), hipMemcpyHostToDevice, s.stream));
+            HIPCHK(life::launch_set_cells(s.lay, d->nx, d->ny, reinterpret_cast<const int64_t *>(stage), m, alive,
+                                          s.buf[s.cur], s.stream));
+        }
+        for (Shard &s : d->shards) {
+            HIPCHK(hipSetDevice(s.device));
+            HIPCHK(hipStreamSynchronize(s.stream));
+        }
+    }
+    // Every apron is refilled K deep from the edited blocks, FILL ops and the
+    // self-wrapped x-apron included; a part-used deep halo (d->since > 0) held
+    // cells advanced from the state before the edit: exchange() restarts it.
+    CHK(exchange(d, 0, false));
+    return life_dev_sync(d);
+}
+
+namespace {
+// The pieces of the periodic interval [a, a + len) (a in [0, n), len <= n)
+// inside the block [b0, b0 + bl): at most two, the block seen at b0 and at
+// b0 + n.  out: window offset, block offset, length.
+struct Span {
+    int64_t win, blk, len;
+};
+int wrapped_spans(int64_t a, int64_t len, int64_t n, int64_t b0, int64_t bl, Span out[2]) {
+    int k = 0;
+    for (int64_t shift = 0; shift <= n; shift += n) {
+        const int64_t lo = std::max(a, b0 + shift), hi = std::min(a + len, b0 + shift + bl);
+        if (hi > lo) out[k++] = Span{lo - a, lo - b0 - shift, hi - lo};
+    }
+    return k;
+}
+int64_t floor_mod(int64_t v, int64_t n) {
+    const int64_t r = v % n;
+    return r < 0 ? r + n : r;
+}
+// A shard whose readout is combined with the other ranks' over RCCL.
+bool reduces(const life_dev *d, const Shard &s) { return d->rank_mode && s.comm; }
+}  // namespace
+
+int life_dev_gather_rect(life_dev *d, int64_t x0, int64_t y0, int64_t w, int64_t h, uint8_t *cells) {
+    if (!d || !cells || w < 1 || h < 1 || w > d->nx || h > d->ny) return LIFE_EINVAL;
+    CHK(life_dev_sync(d));
+    const int64_t ax = floor_mod(x0, d->nx), ay = floor_mod(y0, d->ny);
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        const life_layout &L = s.lay;
+        Span sx[2], sy[2];
+        const int kx = wrapped_spans(ax, w, d->nx, L.x0, L.w, sx), ky = wrapped_spans(ay, h, d->ny, L.y0, L.h, sy);
+        // the window in device memory, row pitch w: this shard's pieces in place
+        uint8_t *win;
+        CHK(stage_buffer(s, (size_t)(w * h), &win));
+        const bool red = reduces(d, s);
+        if (red) HIPCHK(hipMemsetAsync(win, 0, (size_t)(w * h), s.stream));
+        for (int j = 0; j < ky; j++)
+            for (int i = 0; i < kx; i++)
+                HIPCHK(life::launch_rect_piece(L, s.buf[s.cur], sx[i].blk, sy[j].blk, sx[i].len, sy[j].len,
+                                               win + sy[j].win * w + sx[i].win, w, s.stream));
+        if (red) {
+            // rank mode: every rank's pieces summed into every rank's window (as census())
+            NCCLCHK(ncclAllReduce(win, win, (size_t)(w * h), ncclUint8, ncclSum, s.comm, s.stream));
+            HIPCHK(hipMemcpyAsync(cells, win, (size_t)(w * h), hipMemcpyDeviceToHost, s.stream));
+            CHK(bounded_sync(s, "gather_rect all-reduce", -1));
+            continue;
+        }
+        // `cells` is the caller's pageable memory: each copy ordered on the
+        // stream that produced the piece, and waited for
+        for (int j = 0; j < ky; j++)
+            for (int i = 0; i < kx; i++) {
+                const size_t off = (size_t)(sy[j].win * w + sx[i].win);
+                HIPCHK(hipMemcpy2DAsync(cells + off, (size_t)w, win + off, (size_t)w, (size_t)sx[i].len,
+                                        (size_t)sy[j].len, hipMemcpyDeviceToHost, s.stream));
+            }
+        HIPCHK(hipStreamSynchronize(s.stream));
+    }
+    return LIFE_OK;
+}
+
+int life_dev_gather_density(life_dev *d, int64_t fx, int64_t fy, uint32_t *counts) {
+    if (!d || !counts || fx < 1 || fy < 1) return LIFE_EINVAL;
+    if ((unsigned __int128)fx * (unsigned __int128)fy >= ((unsigned __int128)1 << 32)) return LIFE_EINVAL;
+    if (fx > d->nx) fx = d->nx;  // factors beyond the grid: one bin
+    if (fy > d->ny) fy = d->ny;
+    CHK(life_dev_sync(d));
+    const int64_t bw = (d->nx + fx - 1) / fx, bh = (d->ny + fy - 1) / fy;
+    const size_t nbins = (size_t)(bw * bh);
+    std::vector<uint32_t> part_map;  // in-process shards after the first: added on the host
+    bool first = true;
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        uint8_t *stage;
+        CHK(stage_buffer(s, nbins * sizeof(uint32_t), &stage));
+        uint32_t *map = reinterpret_cast<uint32_t *>(stage);
+        HIPCHK(hipMemsetAsync(map, 0, nbins * sizeof(uint32_t), s.stream));
+        HIPCHK(life::launch_density(s.lay, s.buf[s.cur], fx, fy, bw, map, s.stream));
+        if (reduces(d, s))
+            NCCLCHK(ncclAllReduce(map, map, nbins, ncclUint32, ncclSum, s.comm, s.stream));
+        uint32_t *dst = counts;
+        if (!first) {
+            part_map.resize(nbins);
+            dst = part_map.data();
+        }
+        HIPCHK(hipMemcpyAsync(dst, map, nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+        CHK(bounded_sync(s, "gather_density all-reduce", -1));
+        if (!first)
+            for (size_t k = 0; k < nbins; k++) counts[k] += part_map[k];
+        first = false;
+    }
+    return LIFE_OK;
+}
+
 int life_dev_layout(life_dev *d, int local_shard, life_layout *out) {
     if (!d || !out || local_shard < 0 || local_shard >= (int)d->shards.size()) return LIFE_EINVAL;
     *out = d->shards[local_shard].lay;

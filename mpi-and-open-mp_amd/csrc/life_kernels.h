@@ -219,6 +219,20 @@ hipError_t launch_fill_random(const life_layout &L, int64_t nx, uint64_t key, ui
 hipError_t launch_census(const life_layout &L, int64_t nx, const uint8_t *buf, unsigned long long *out,
                          hipStream_t s);
 
+// Sparse edits: the n (x, y) pairs of `xy` (device memory, global
+// coordinates, wrapped with a true modulo) that fall in the block become
+// alive or dead; other cells, the aprons and the pad bits stay as they are.
+hipError_t launch_set_cells(const life_layout &L, int64_t nx, int64_t ny, const int64_t *xy, int64_t n, int alive,
+                            uint8_t *buf, hipStream_t s);
+// Block cells [lx0, lx0 + pw) x [ly0, ly0 + ph) (owned) as 0/1 bytes at
+// out[j * opitch + i].
+hipError_t launch_rect_piece(const life_layout &L, const uint8_t *buf, int64_t lx0, int64_t ly0, int64_t pw,
+                             int64_t ph, uint8_t *out, int64_t opitch, hipStream_t s);
+// Adds the block's live cells to the density map: map[(y / fy) * bw + x / fx]
+// over global (x, y); bw = bins per map row.
+hipError_t launch_density(const life_layout &L, const uint8_t *buf, int64_t fx, int64_t fy, int64_t bw,
+                          uint32_t *map, hipStream_t s);
+
 // Copy-ceiling probe: out[0, bytes) = in[0, bytes), bytes a multiple of 16.
 hipError_t launch_copy(const void *in, void *out, int64_t bytes, hipStream_t s);
 

@@ -1624,6 +1624,144 @@ __global__ void census_kernel(const uint8_t *buf, int64_t pitch, int64_t ya, int
     }
 }
 
+// Sparse edits (life_dev_set_cells): one thread per (x, y) pair of the staged
+// list; coordinates wrap with a true modulo and only the cells of this block
+// are written -- an atomic OR / AND on the owning dword of the pair layout
+// (two listed cells may share a dword), a byte store for byte cells.  Aprons
+// and the pad bits past w are not touched: the caller refills the halo.
+__device__ __forceinline__ int64_t wrap_mod(int64_t v, int64_t n) {
+    const int64_t r = v % n;
+    return r < 0 ? r + n : r;
+}
+template <bool BIT>
+__global__ void set_cells_kernel(uint8_t *buf, int64_t pitch, int64_t ya, int64_t xoff, int64_t w, int64_t h,
+                                 int64_t gx0, int64_t gy0, int64_t nx, int64_t ny, const int64_t *xy, int64_t n,
+                                 int alive) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t x = wrap_mod(xy[2 * i], nx) - gx0, y = wrap_mod(xy[2 * i + 1], ny) - gy0;
+    if (x < 0 || x >= w || y < 0 || y >= h) return;
+    uint8_t *row = buf + (y + ya) * pitch + xoff;
+    if (BIT) {
+        uint32_t *wd = reinterpret_cast<uint32_t *>(row) + pair_dword(x);
+        const uint32_t m = 1u << pair_bit(x);
+        if (alive)
+            atomicOr(wd, m);
+        else
+            atomicAnd(wd, ~m);
+    } else {
+        row[x] = alive ? 1 : 0;
+    }
+}
+
+// A window piece (life_dev_gather_rect): block cells [lx0, lx0 + pw) x
+// [ly0, ly0 + ph) as 0/1 bytes at out[j * opitch + i], read straight from the
+// padded layout.  One thread per 8 output cells of a row; 2-D grid, y strides
+// rows.  Bit encoding: the pair holding the first cell in natural order
+// (nat64), funnel-shifted with the next pair when the 8 cells straddle it
+// (that pair is read only then, and is owned: the cells are).
+template <bool BIT>
+__global__ void rect_kernel(const uint8_t *buf, int64_t pitch, int64_t ya, int64_t xoff, int64_t lx0, int64_t ly0,
+                            int64_t pw, int64_t ph, uint8_t *out, int64_t opitch) {
+    const int64_t i0 = 8 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    if (i0 >= pw) return;
+    const int n = pw - i0 < 8 ? (int)(pw - i0) : 8;
+    const int64_t x = lx0 + i0;
+    for (int64_t j = blockIdx.y; j < ph; j += gridDim.y) {
+        const uint8_t *row = buf + (ly0 + j + ya) * pitch + xoff;
+        uint32_t c;  // cell k at bit k
+        if (BIT) {
+            const uint32_t *wd = reinterpret_cast<const uint32_t *>(row);
+            const int64_t pp = x >> 6;
+            const uint32_t sh = (uint32_t)(x & 63);
+            uint64_t v = pair_nat(wd, pp) >> sh;
+            if (sh + (uint32_t)n > 64u) v |= pair_nat(wd, pp + 1) << (64 - sh);
+            c = (uint32_t)v;
+        } else {
+            c = 0;
+            for (int k = 0; k < n; ++k) c |= (uint32_t)(row[x + k] & 1u) << k;
+        }
+        uint8_t *o = out + j * opitch + i0;
+        for (int k = 0; k < n; ++k) o[k] = (uint8_t)((c >> k) & 1u);
+    }
+}
+
+// Density map (life_dev_gather_density): map[by * bw + bx] += live owned cells
+// with global x / fx == bx and y / fy == by.  Shaped like the census -- a lane
+// per 16-byte unit column, one uint4 load per lane and row -- but block y
+// walks `rpb` CONSECUTIVE rows, so a lane counts down the rows of one bin row
+// in registers.  The lane splits its unit over the bins it touches with
+// masks built once: bin cells [c0, c1) of the unit keep, in dword k, the bits
+// below_k(c1) & ~below_k(c0), below_k(c) = the dword's cells under c -- for
+// the interleaved pairs (c + 1) >> 1 bits of an even dword and c >> 1 of an
+// odd one (c counted from the pair's first cell), for byte cells 8 bits per
+// cell; cells past w fall outside every [c0, c1).  Bins are taken two at a
+// time (a unit of fx >= CPU cells touches at most two: one pass over the
+// rows; smaller factors re-read the rows once per further bin pair, from
+// cache), and each (unit, bin, bin row) ends in ONE atomicAdd.  A wave whose
+// lanes all lie in one bin adds up across the wave first and lane 0 issues
+// the atomic.  Lanes past the last unit of a partly filled wave shadow lane
+// 0's column with empty masks, so the wave stays convergent.
+__device__ __forceinline__ uint32_t low_mask(int64_t n) {  // the n lowest bits, n clamped to 0..32
+    return n <= 0 ? 0u : n >= 32 ? 0xFFFFFFFFu : (0xFFFFFFFFu >> (32 - n));
+}
+template <int CPU>
+__device__ __forceinline__ uint32_t cells_below(int k, int64_t c) {  // dword k's bits of unit cells [0, c)
+    if (CPU == 16) return low_mask(8 * (c - 4 * k)) & 0x01010101u;
+    return low_mask((c - 64 * (k >> 1) - (k & 1) + 1) >> 1);
+}
+template <int CPU>
+__global__ __launch_bounds__(256) void density_kernel(const uint8_t *buf, int64_t pitch, int64_t ya, int64_t xoff,
+                                                      int64_t w, int64_t h, int64_t units, int64_t gx0, int64_t gy0,
+                                                      int64_t fx, int64_t fy, int64_t bw, int64_t rpb,
+                                                      uint32_t *map) {
+    const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t u0 = u - (threadIdx.x & 63);  // the wave's first unit
+    if (u0 >= units) return;                    // a whole wave past the row
+    const bool live = u < units;
+    const int64_t uu = live ? u : u0;
+    const int64_t left = w - uu * CPU;
+    const int64_t valid = !live ? 0 : left < CPU ? left : CPU;  // cells of this unit inside the block
+    const int64_t gxu = gx0 + uu * CPU;
+    const int64_t bfirst = gxu / fx, blast = live ? (gxu + valid - 1) / fx : bfirst;
+    const bool one = __all(blast == bfirst && bfirst == __shfl(bfirst, 0)) != 0;  // the wave shares one bin
+    const int64_t r0 = (int64_t)blockIdx.y * rpb, r1 = r0 + rpb < h ? r0 + rpb : h;
+    const uint8_t *col = buf + ya * pitch + xoff + 16 * uu;
+    for (int64_t b = bfirst; b <= blast; b += 2) {
+        uint32_t ma[4], mb[4];
+        {
+            const int64_t e0 = b * fx - gxu, e1 = e0 + fx, e2 = e1 + fx;  // bin edges, in unit cells
+            const int64_t c0 = e0 < 0 ? 0 : e0 > valid ? valid : e0, c1 = e1 < 0 ? 0 : e1 > valid ? valid : e1;
+            const int64_t c2 = e2 < 0 ? 0 : e2 > valid ? valid : e2;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t l0 = cells_below<CPU>(k, c0), l1 = cells_below<CPU>(k, c1);
+                ma[k] = l1 & ~l0;
+                mb[k] = cells_below<CPU>(k, c2) & ~l1;
+            }
+        }
+        for (int64_t y = r0; y < r1;) {
+            const int64_t by = (gy0 + y) / fy;
+            const int64_t lim = (by + 1) * fy - gy0, ye = lim < r1 ? lim : r1;  // rows [y, ye) share bin row by
+            uint32_t ca = 0, cb = 0;
+#pragma unroll 4
+            for (; y < ye; ++y) {
+                const uint4 q = *reinterpret_cast<const uint4 *>(col + y * pitch);
+                ca += __popc(q.x & ma[0]) + __popc(q.y & ma[1]) + __popc(q.z & ma[2]) + __popc(q.w & ma[3]);
+                cb += __popc(q.x & mb[0]) + __popc(q.y & mb[1]) + __popc(q.z & mb[2]) + __popc(q.w & mb[3]);
+            }
+            uint32_t *o = map + by * bw + b;
+            if (one) {  // cb == 0: the unit ends inside bin b
+                for (int s = 32; s > 0; s >>= 1) ca += __shfl_xor(ca, s);
+                if ((threadIdx.x & 63) == 0 && ca) atomicAdd(o, ca);
+            } else {
+                if (ca) atomicAdd(o, ca);
+                if (cb) atomicAdd(o + 1, cb);
+            }
+        }
+    }
+}
+
 inline bool is_bit(const life_layout &L) { return L.kernel == LIFE_KERNEL_BIT; }
 inline unsigned blocks_for(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
@@ -2411,6 +2549,50 @@ hipError_t launch_census(const life_layout &L, int64_t nx, const uint8_t *buf, u
     else
         census_kernel<16><<<grid, 256, 0, s>>>(buf, L.pitch, L.yapron, L.xoff, L.w, L.h, L.units, L.x0, L.y0, nx,
                                                 out);
+    return hipGetLastError();
+}
+
+hipError_t launch_set_cells(const life_layout &L, int64_t nx, int64_t ny, const int64_t *xy, int64_t n, int alive,
+                            uint8_t *buf, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    const unsigned g = blocks_for(n, 256);
+    if (is_bit(L))
+        set_cells_kernel<true><<<g, 256, 0, s>>>(buf, L.pitch, L.yapron, L.xoff, L.w, L.h, L.x0, L.y0, nx, ny, xy, n,
+                                                 alive);
+    else
+        set_cells_kernel<false><<<g, 256, 0, s>>>(buf, L.pitch, L.yapron, L.xoff, L.w, L.h, L.x0, L.y0, nx, ny, xy, n,
+                                                  alive);
+    return hipGetLastError();
+}
+
+hipError_t launch_rect_piece(const life_layout &L, const uint8_t *buf, int64_t lx0, int64_t ly0, int64_t pw,
+                             int64_t ph, uint8_t *out, int64_t opitch, hipStream_t s) {
+    if (lx0 < 0 || ly0 < 0 || pw < 1 || ph < 1 || lx0 + pw > L.w || ly0 + ph > L.h) return hipErrorInvalidValue;
+    const dim3 grid(blocks_for((pw + 7) / 8, 256), (unsigned)(ph < 8192 ? ph : 8192));
+    if (is_bit(L))
+        rect_kernel<true><<<grid, 256, 0, s>>>(buf, L.pitch, L.yapron, L.xoff, lx0, ly0, pw, ph, out, opitch);
+    else
+        rect_kernel<false><<<grid, 256, 0, s>>>(buf, L.pitch, L.yapron, L.xoff, lx0, ly0, pw, ph, out, opitch);
+    return hipGetLastError();
+}
+
+hipError_t launch_density(const life_layout &L, const uint8_t *buf, int64_t fx, int64_t fy, int64_t bw,
+                          uint32_t *map, hipStream_t s) {
+    if (fx < 1 || fy < 1 || bw < 1) return hipErrorInvalidValue;
+    // rows per block: about two lanes per hardware thread slot of the chip
+    // (256 CUs x 2048), at most 65535 blocks in y
+    const int64_t bx = blocks_for(L.units, 256);
+    int64_t chunks = (int64_t)(2 * 256 * 2048) / (bx * 256);
+    chunks = chunks < 1 ? 1 : chunks > L.h ? L.h : chunks;
+    if (chunks > 65535) chunks = 65535;
+    const int64_t rpb = (L.h + chunks - 1) / chunks;
+    const dim3 grid((unsigned)bx, (unsigned)((L.h + rpb - 1) / rpb));
+    if (is_bit(L))
+        density_kernel<128><<<grid, 256, 0, s>>>(buf, L.pitch, L.yapron, L.xoff, L.w, L.h, L.units, L.x0, L.y0, fx, fy,
+                                                  bw, rpb, map);
+    else
+        density_kernel<16><<<grid, 256, 0, s>>>(buf, L.pitch, L.yapron, L.xoff, L.w, L.h, L.units, L.x0, L.y0, fx, fy,
+                                                 bw, rpb, map);
     return hipGetLastError();
 }
 

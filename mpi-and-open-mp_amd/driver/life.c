@@ -21,6 +21,16 @@
  *   --no-vtk          skip frame output (timing runs)
  *   --format vtk|bits frame format: the reference's VTK text (default) or a
  *                     packed binary dump vtk/life_%06d.bits (checkpoint)
+ *   --format density:FX[xFY]   frames are block-summed live counts
+ *                     (life_dev_gather_density): vtk/life_%06d.dens holds the
+ *                     line "LIFEDENS 1 nx ny fx fy generation\n", then
+ *                     ceil(ny/FY) rows of ceil(nx/FX) little-endian uint32;
+ *                     FY defaults to FX; only the map is allocated for frames
+ *   --sparse          the .cfg cells go to the device as a coordinate list
+ *                     (life_dev_clear + life_dev_set_cells): the nx*ny host
+ *                     grid is never allocated; same cells, same frames.  With
+ *                     --format density a pattern in a 65536^2 universe needs
+ *                     kilobytes on the host
  *   --resume FILE     start from a .bits dump instead of the .cfg cells
  *   --live            print the live-cell count after the run to stderr
  *   --rank-mode       one-process-per-GPU mode even without a launcher (world 1)
@@ -73,6 +83,8 @@ static int64_t wrapi(int64_t i, int64_t n) { return ((i % n) + n) % n; }
 typedef struct {
     int64_t steps, save_steps, nx, ny;
     uint8_t *grid; /* nx*ny 0/1 cells, row-major (NULL until loaded) */
+    int64_t *cells; /* --sparse: ncells (i, j) pairs as written in the file, instead of grid */
+    int64_t ncells;
 } cfg_t;
 
 /* .cfg loader: life_cart.c:92-111.  "steps\n save_steps\n nx ny\n" then one
@@ -135,7 +147,29 @@ static void *parse_cells(void *arg) {
     return NULL;
 }
 
-static int load_cfg(const char *path, cfg_t *c, int64_t o_nx, int64_t o_ny) {
+/* --sparse: the cell lines as a list of (i, j) pairs, unwrapped
+ * (life_dev_set_cells wraps them); tokens pair up across lines like the
+ * reference's fscanf loop. */
+static int parse_cell_list(const char *p, const char *end, cfg_t *c) {
+    int64_t cap = 0;
+    for (;;) {
+        long long v[2];
+        int r = next_int(&p, end, &v[0]);
+        if (r == 0) return LIFE_OK;
+        if (r < 0 || next_int(&p, end, &v[1]) != 1) return LIFE_EIO;
+        if (c->ncells == cap) {
+            cap = cap ? 2 * cap : 1024;
+            int64_t *q = (int64_t *)realloc(c->cells, (size_t)cap * 2 * sizeof *q);
+            if (!q) return LIFE_ENOMEM;
+            c->cells = q;
+        }
+        c->cells[2 * c->ncells] = v[0];
+        c->cells[2 * c->ncells + 1] = v[1];
+        c->ncells++;
+    }
+}
+
+static int load_cfg(const char *path, cfg_t *c, int64_t o_nx, int64_t o_ny, int sparse) {
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return LIFE_EIO;
     struct stat st;
@@ -158,10 +192,14 @@ static int load_cfg(const char *path, cfg_t *c, int64_t o_nx, int64_t o_ny) {
         c->save_steps = v[1];
         c->nx = o_nx > 0 ? o_nx : v[2]; /* --nx/--ny override the header before the cells wrap */
         c->ny = o_ny > 0 ? o_ny : v[3];
-        c->grid = (uint8_t *)calloc((size_t)(c->nx * c->ny), 1);
-        if (!c->grid) rc = LIFE_ENOMEM;
+        if (!sparse) {
+            c->grid = (uint8_t *)calloc((size_t)(c->nx * c->ny), 1);
+            if (!c->grid) rc = LIFE_ENOMEM;
+        }
     }
-    if (rc == LIFE_OK) {
+    if (rc == LIFE_OK && sparse) {
+        rc = parse_cell_list(p, end, c);
+    } else if (rc == LIFE_OK) {
         enum { kMaxThreads = 16 };
         long np = sysconf(_SC_NPROCESSORS_ONLN);
         int nt = (int)((size_t)(end - p) / (1 << 22)); /* >= 4 MiB per thread */
@@ -198,7 +236,10 @@ static int load_cfg(const char *path, cfg_t *c, int64_t o_nx, int64_t o_ny) {
     if (len) munmap((void *)base, len);
     if (rc != LIFE_OK) {
         free(c->grid);
+        free(c->cells);
         c->grid = NULL;
+        c->cells = NULL;
+        c->ncells = 0;
     }
     return rc;
 }
@@ -242,6 +283,20 @@ static int save_bits(const char *path, int64_t nx, int64_t ny, int64_t gen, cons
     return fclose(f) == 0 && ok ? LIFE_OK : LIFE_EIO;
 }
 
+/* Density frame (extension): "LIFEDENS 1 <nx> <ny> <fx> <fy> <generation>\n",
+ * then ceil(ny/fy) rows of ceil(nx/fx) uint32 live counts as
+ * life_dev_gather_density wrote them (little-endian hosts). */
+static int save_density(const char *path, int64_t nx, int64_t ny, int64_t fx, int64_t fy, int64_t gen,
+                        const uint32_t *counts) {
+    FILE *f = open_frame(path);
+    if (!f) return LIFE_EIO;
+    fprintf(f, "LIFEDENS 1 %lld %lld %lld %lld %lld\n", (long long)nx, (long long)ny, (long long)fx, (long long)fy,
+            (long long)gen);
+    const size_t n = (size_t)(((nx + fx - 1) / fx) * ((ny + fy - 1) / fy));
+    const int ok = fwrite(counts, sizeof *counts, n, f) == n;
+    return fclose(f) == 0 && ok ? LIFE_OK : LIFE_EIO;
+}
+
 static int load_bits(const char *path, int64_t *nx, int64_t *ny, int64_t *gen, uint8_t **grid) {
     FILE *f = fopen(path, "r");
     if (!f) return LIFE_EIO;
@@ -275,7 +330,8 @@ static int load_bits(const char *path, int64_t *nx, int64_t *ny, int64_t *gen, u
 int main(int argc, char **argv) {
     const char *cfg_path = NULL, *resume = NULL;
     int gpus = 1, kernel = LIFE_KERNEL_BIT, vtk = 1, live = 0, have_random = 0, bits = 0, force_rank = 0;
-    int partition = LIFE_PARTITION_CART;
+    int partition = LIFE_PARTITION_CART, sparse = 0;
+    long long dfx = 0, dfy = 0; /* --format density:FX[xFY] (bits == 2) */
     long long o_nx = -1, o_ny = -1, o_steps = -1, o_save = -1;
     unsigned long long seed = 0;
     double density = 0.5;
@@ -314,7 +370,14 @@ int main(int argc, char **argv) {
         else if (!strcmp(s, "--format") && more) {
             const char *fm = argv[++a];
             bits = !strcmp(fm, "bits") ? 1 : !strcmp(fm, "vtk") ? 0 : -1;
-        } else if (!strcmp(s, "--resume") && more) resume = argv[++a];
+            if (!strncmp(fm, "density:", 8)) {
+                char *end;
+                dfx = dfy = strtoll(fm + 8, &end, 10);
+                if (*end == 'x') dfy = strtoll(end + 1, &end, 10);
+                bits = !*end && end != fm + 8 && dfx >= 1 && dfy >= 1 ? 2 : -1;
+            }
+        } else if (!strcmp(s, "--sparse")) sparse = 1;
+        else if (!strcmp(s, "--resume") && more) resume = argv[++a];
         else if (!strcmp(s, "--live")) live = 1;
         else if (!strcmp(s, "--rank-mode")) force_rank = 1;
         else if (s[0] != '-' && !cfg_path) cfg_path = s;
@@ -348,8 +411,8 @@ int main(int argc, char **argv) {
     }
     const int root = world - 1; /* life_collect's root: cart rank (dims0-1, dims1-1) = size-1 */
 
-    cfg_t c = {0, 1, 0, 0, NULL};
-    if (cfg_path && load_cfg(cfg_path, &c, resume ? -1 : o_nx, resume ? -1 : o_ny) != LIFE_OK) {
+    cfg_t c = {0, 1, 0, 0, NULL, NULL, 0};
+    if (cfg_path && load_cfg(cfg_path, &c, resume ? -1 : o_nx, resume ? -1 : o_ny, sparse) != LIFE_OK) {
         fprintf(stderr, "life_mi355x: cannot read config '%s'\n", cfg_path);
         return 1;
     }
@@ -401,7 +464,15 @@ int main(int argc, char **argv) {
     const int writer = !rank_mode || rank == root; /* the process that writes frames and prints */
     uint8_t *grid = NULL; /* packed rows: bits frames */
     char *body = NULL;    /* VTK cell text */
-    if (vtk && bits && writer) {
+    uint32_t *dens = NULL; /* density map (every rank: the readout is collective and lands on all) */
+    int64_t fx = dfx, fy = dfy;
+    if (vtk && bits == 2) {
+        if (fx > c.nx) fx = c.nx; /* factors beyond the grid: one bin */
+        if (fy > c.ny) fy = c.ny;
+        dens = (uint32_t *)calloc((size_t)(((c.nx + fx - 1) / fx) * ((c.ny + fy - 1) / fy)), sizeof *dens);
+        if (!dens) die("host density map", LIFE_ENOMEM);
+    }
+    if (vtk && bits == 1 && writer) {
         grid = (uint8_t *)calloc((size_t)(c.ny * ((c.nx + 7) / 8)), 1);
         if (!grid) die("host grid", LIFE_ENOMEM);
     }
@@ -414,12 +485,16 @@ int main(int argc, char **argv) {
         free(resumed);
     } else if (have_random) {
         rc = life_dev_fill_random(d, seed, density >= 1.0 ? 0xFFFFFFFFu : (uint32_t)(density * 4294967296.0));
+    } else if (sparse) {
+        if ((rc = life_dev_clear(d)) == LIFE_OK) rc = life_dev_set_cells(d, c.cells, c.ncells, 1);
     } else {
         rc = life_dev_upload(d, c.grid);
     }
     if (rc) die("init", rc);
     free(c.grid);
+    free(c.cells);
     c.grid = NULL;
+    c.cells = NULL;
 
     /* life_cart.c:62-80: the timer starts after init and covers the frame
      * collects + VTK writes and every generation.  Generations and frame
@@ -431,8 +506,15 @@ int main(int argc, char **argv) {
     for (int64_t i = gen0; i < c.steps;) {
         const int save = vtk && i % c.save_steps == 0;
         if (save) { /* collect (blocking, every rank), then write it while the GPU steps on */
-            if ((rc = bits ? life_dev_gather_bits(d, grid) : life_dev_gather_vtk(d, body))) die("gather", rc);
-            snprintf(path, sizeof path, bits ? "vtk/life_%06lld.bits" : "vtk/life_%06lld.vtk", (long long)i);
+            if ((rc = bits == 2   ? life_dev_gather_density(d, fx, fy, dens)
+                      : bits == 1 ? life_dev_gather_bits(d, grid)
+                                  : life_dev_gather_vtk(d, body)))
+                die("gather", rc);
+            snprintf(path, sizeof path,
+                     bits == 2   ? "vtk/life_%06lld.dens"
+                     : bits == 1 ? "vtk/life_%06lld.bits"
+                                 : "vtk/life_%06lld.vtk",
+                     (long long)i);
         }
         int64_t n = c.steps - i;
         if (vtk) {
@@ -440,7 +522,10 @@ int main(int argc, char **argv) {
             if (to_save < n) n = to_save;
         }
         if ((rc = life_dev_step(d, n))) die("step", rc); /* asynchronous */
-        if (save && writer && (rc = bits ? save_bits(path, c.nx, c.ny, i, grid) : save_vtk(path, c.nx, c.ny, body)))
+        if (save && writer &&
+            (rc = bits == 2   ? save_density(path, c.nx, c.ny, fx, fy, i, dens)
+                  : bits == 1 ? save_bits(path, c.nx, c.ny, i, grid)
+                              : save_vtk(path, c.nx, c.ny, body)))
             die(path, rc);
         i += n;
     }
@@ -455,5 +540,6 @@ int main(int argc, char **argv) {
     life_dev_destroy(d);
     free(grid);
     free(body);
+    free(dens);
     return 0;
 }

@@ -29,7 +29,8 @@ import sys
 
 import numpy as np
 
-from .cfg import bits_bytes, load_bits, load_cfg, save_vtk, vtk_bytes, vtk_header  # noqa: F401
+from .cfg import (bits_bytes, density_bytes, load_bits, load_cfg, load_cfg_cells, load_density,  # noqa: F401
+                  save_vtk, vtk_bytes, vtk_header)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # LIFE_MI355X_LIB: load another build of the same library (experiments only)
@@ -62,6 +63,7 @@ ABI_SYMBOLS = (
     "life_dev_gather_vtk", "life_dev_gather_bits", "life_dev_destroy", "life_measure_copy", "life_dev_phase_stats",
     "life_dev_barrier", "life_device_count", "life_dev_last_path", "life_dev_call_stats",
     "life_dev_strerror", "life_dev_shard_info",
+    "life_dev_clear", "life_dev_set_cells", "life_dev_gather_rect", "life_dev_gather_density",
 )
 PATHS = {0: "none", 1: "onegen", 2: "tiles", 3: "flow", 5: "small"}
 
@@ -142,6 +144,10 @@ def _lib():
         L.life_dev_gather.argtypes = [vp, P(ctypes.c_uint8)]
         L.life_dev_gather_vtk.argtypes = [vp, ctypes.c_char_p]
         L.life_dev_gather_bits.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8)]
+        L.life_dev_clear.argtypes = [vp]
+        L.life_dev_set_cells.argtypes = [vp, P(i64), i64, i32]
+        L.life_dev_gather_rect.argtypes = [vp, i64, i64, i64, i64, P(ctypes.c_uint8)]
+        L.life_dev_gather_density.argtypes = [vp, i64, i64, P(ctypes.c_uint32)]
         L.life_dev_live_count.argtypes = [vp]
         L.life_dev_live_count.restype = i64
         L.life_dev_sync.argtypes = [vp]
@@ -323,6 +329,44 @@ class Life:
 
     def fill_random(self, seed: int, density: float = 0.5) -> None:
         _check(_lib().life_dev_fill_random(self._h, seed, density_to_thr(density)), "fill_random")
+
+    # sparse I/O: no nx*ny host grid (life_dev_clear / set_cells / gather_rect / gather_density)
+    def clear(self) -> None:
+        """Every cell dead (== upload of an all-zero grid)."""
+        _check(_lib().life_dev_clear(self._h), "clear")
+
+    def set_cells(self, cells, alive: bool = True) -> None:
+        """The listed (x, y) cells become alive (or dead); coordinates wrap
+        periodically, duplicates are allowed, other cells are untouched."""
+        c = np.ascontiguousarray(np.asarray(cells, dtype=np.int64))
+        if c.ndim != 2 or c.shape[1] != 2:
+            raise ValueError(f"set_cells: cells must have shape (n, 2), not {c.shape}")
+        _check(_lib().life_dev_set_cells(self._h, c.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), c.shape[0],
+                                         1 if alive else 0), "set_cells")
+
+    def gather_rect(self, x0: int, y0: int, w: int, h: int, out: np.ndarray | None = None) -> np.ndarray:
+        """The periodic w x h window at (x0, y0) as an (h, w) uint8 array:
+        out[j, i] is cell ((x0 + i) mod nx, (y0 + j) mod ny)."""
+        w, h = int(w), int(h)
+        if out is None:
+            out = _host_buffer((max(h, 0), max(w, 0)))
+        if out.shape != (max(h, 0), max(w, 0)) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError("gather_rect: out must be a C-contiguous uint8 (h, w) array")
+        _check(_lib().life_dev_gather_rect(self._h, int(x0), int(y0), w, h,
+                                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))), "gather_rect")
+        return out
+
+    def gather_density(self, fx: int, fy: int | None = None) -> np.ndarray:
+        """Block-summed live counts: a (ceil(ny/fy), ceil(nx/fx)) uint32 array,
+        bin [by, bx] counting the live cells with x // fx == bx, y // fy == by."""
+        fx = int(fx)
+        fy = fx if fy is None else int(fy)
+        # factors the library rejects (LIFE_EINVAL) have no map shape: it never writes
+        shape = (-(-self.ny // fy), -(-self.nx // fx)) if fx >= 1 and fy >= 1 else (1, 1)
+        out = _host_buffer(shape + (4,)).view(np.uint32).reshape(shape)
+        _check(_lib().life_dev_gather_density(self._h, fx, fy, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
+               "gather_density")
+        return out
 
     def step(self, generations: int = 1) -> None:
         _check(_lib().life_dev_step(self._h, generations), "step")

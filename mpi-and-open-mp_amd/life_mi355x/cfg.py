@@ -7,6 +7,9 @@
   forever as the reference's fscanf loop does.
 * ``save_vtk`` / ``vtk_bytes`` restate life_save_vtk (life_cart.c:159-187):
   ASCII STRUCTURED_POINTS, one ``%d\\n`` per cell, y outer, x inner.
+* ``load_cfg_cells`` is the same parser without the grid: the coordinate list
+  for ``Life.set_cells``; ``density_bytes`` / ``load_density`` are the
+  driver's density-map frames.
 """
 from __future__ import annotations
 
@@ -15,8 +18,8 @@ import os
 import numpy as np
 
 
-def load_cfg(path: str):
-    """-> (steps, save_steps, grid[ny, nx] uint8)."""
+def _parse_cfg(path: str):
+    """-> (steps, save_steps, nx, ny, cells[n, 2] int64 as written in the file)."""
     with open(path, "r") as f:
         toks = f.read().split()
     try:
@@ -28,11 +31,23 @@ def load_cfg(path: str):
     steps, save_steps, nx, ny = vals[:4]
     if nx <= 0 or ny <= 0:
         raise ValueError(f"{path}: bad grid size {nx}x{ny}")
+    return steps, save_steps, nx, ny, np.asarray(vals[4:], dtype=np.int64).reshape(-1, 2)
+
+
+def load_cfg(path: str):
+    """-> (steps, save_steps, grid[ny, nx] uint8)."""
+    steps, save_steps, nx, ny, c = _parse_cfg(path)
     grid = np.zeros((ny, nx), dtype=np.uint8)
-    if len(vals) > 4:
-        c = np.asarray(vals[4:], dtype=np.int64).reshape(-1, 2)
-        grid[np.mod(c[:, 1], ny), np.mod(c[:, 0], nx)] = 1  # u0[ind(i, j)] = 1
+    grid[np.mod(c[:, 1], ny), np.mod(c[:, 0], nx)] = 1  # u0[ind(i, j)] = 1
     return steps, save_steps, grid
+
+
+def load_cfg_cells(path: str):
+    """-> (steps, save_steps, nx, ny, cells[n, 2] int64): the live cells as
+    (x, y) rows, wrapped into the grid, in the file's order and with its
+    duplicates -- the list Life.set_cells takes; no grid is allocated."""
+    steps, save_steps, nx, ny, c = _parse_cfg(path)
+    return steps, save_steps, nx, ny, np.mod(c, np.asarray([nx, ny], dtype=np.int64))
 
 
 def vtk_header(nx: int, ny: int) -> bytes:
@@ -77,6 +92,33 @@ def load_bits(path: str):
         raise ValueError(f"{path}: truncated")
     grid = np.unpackbits(raw.reshape(ny, rb), axis=1, bitorder="little")[:, :nx]
     return gen, np.ascontiguousarray(grid, dtype=np.uint8)
+
+
+def density_bytes(counts: np.ndarray, nx: int, ny: int, fx: int, fy: int, generation: int = 0) -> bytes:
+    """The driver's density frame (--format density:FX[xFY]):
+    'LIFEDENS 1 nx ny fx fy gen\\n' then ceil(ny/fy) rows of ceil(nx/fx)
+    little-endian uint32 live counts (Life.gather_density)."""
+    c = np.asarray(counts)
+    if c.shape != (-(-ny // fy), -(-nx // fx)):
+        raise ValueError(f"density map shape {c.shape} != ({-(-ny // fy)}, {-(-nx // fx)})")
+    return f"LIFEDENS 1 {nx} {ny} {fx} {fy} {generation}\n".encode() + c.astype("<u4").tobytes()
+
+
+def load_density(path: str):
+    """-> (generation, nx, ny, fx, fy, counts[ceil(ny/fy), ceil(nx/fx)] uint32)
+    of a --format density frame."""
+    with open(path, "rb") as f:
+        head = f.readline().split()
+        if len(head) != 7 or head[0] != b"LIFEDENS" or head[1] != b"1":
+            raise ValueError(f"{path}: not a LIFEDENS v1 frame")
+        nx, ny, fx, fy, gen = (int(t) for t in head[2:])
+        if min(nx, ny, fx, fy) < 1:
+            raise ValueError(f"{path}: bad LIFEDENS header")
+        raw = f.read()
+    bw, bh = -(-nx // fx), -(-ny // fy)
+    if len(raw) != 4 * bw * bh:
+        raise ValueError(f"{path}: truncated")
+    return gen, nx, ny, fx, fy, np.frombuffer(raw, dtype="<u4").reshape(bh, bw).astype(np.uint32)
 
 
 def save_vtk(path: str, grid: np.ndarray) -> None:
