@@ -15,7 +15,6 @@
 #include <rccl/rccl.h>
 #include <algorithm>
 #include <stdarg.h>
-#include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -25,6 +24,8 @@
 #include <utility>
 #include <vector>
 
+#include "life_env.h"
+#include "life_io.h"
 #include "life_kernels.h"
 #include "life_mi355x.h"
 
@@ -119,11 +120,7 @@ struct Shard {
 // 20-generation call then runs as two launches of 10 (97.1-97.5 T against
 // 93.5-93.9 for one launch of 20; profiles/r03/r4d).  Byte tiles are HBM-bound below ~32 generations per
 // pass: 32.  LIFE_BLOCK_GENS overrides both at load time; 0 = per encoding.
-static const int kEnvBlockGens = [] {
-    const char *e = getenv("LIFE_BLOCK_GENS");
-    const int v = e ? atoi(e) : 0;
-    return v >= 1 && v <= 32 ? v : 0;
-}();
+static const int kEnvBlockGens = life::env::read(life::env::kBlockGens);
 // LIFE_FLOW (0/1/2/3) sets LIFE_OPT_FLOW's default at load time; default 3,
 // automatic (round 5): the dataflow form where a pass is only a few rounds
 // of resident workgroups, so that a launch per pass would idle the chip in
@@ -135,58 +132,25 @@ static const int kEnvBlockGens = [] {
 // saves: 992 generations at 65536^2, per-launch tiles 109.4-112.9 T against
 // 104.2-108.5 T for the dataflow form at every pass size 10-16
 // (profiles/r03/r4g).
-static const int kEnvFlow = [] {
-    const char *e = getenv("LIFE_FLOW");
-    const int v = e ? atoi(e) : 3;
-    return v >= 0 && v <= 3 ? v : 3;
-}();
-// LIFE_FLOW_AUTO_ROUNDS (measurement knob, default 5): LIFE_OPT_FLOW 3 takes
-// the dataflow form when a pass holds fewer rounds of resident workgroups.
-static const double kFlowAutoRounds = [] {
-    const char *e = getenv("LIFE_FLOW_AUTO_ROUNDS");
-    const double v = e ? atof(e) : 0.0;
-    return v > 0.0 ? v : 5.0;
-}();
+static const int kEnvFlow = life::env::read(life::env::kFlow);
+// LIFE_OPT_FLOW 3 takes the dataflow form when a pass holds fewer rounds of
+// resident workgroups (flow_auto).
+constexpr double kFlowAutoRounds = 5.0;
 // LIFE_DEEP_HALO (0/1, default 1) sets LIFE_OPT_DEEP_HALO's default at load
 // time (generation_block).
-static const bool kEnvDeepHalo = [] {
-    const char *e = getenv("LIFE_DEEP_HALO");
-    return e ? atoi(e) != 0 : true;
-}();
+static const bool kEnvDeepHalo = life::env::read(life::env::kDeepHalo) != 0;
 static int default_block_gens(int kernel) {
     return kEnvBlockGens ? kEnvBlockGens : (kernel == LIFE_KERNEL_BIT ? 12 : 32);
 }
-// LIFE_FLOW_MIN_PASSES (measurement knob, default 4): fewest passes a call
-// runs in the dataflow form
-static const int64_t kFlowMinPasses = [] {
-    const char *e = getenv("LIFE_FLOW_MIN_PASSES");
-    const int v = e ? atoi(e) : 0;
-    return (int64_t)(v >= 2 ? v : 4);
-}();
+// fewest passes a call runs in the dataflow form
+constexpr int64_t kFlowMinPasses = 4;
 // How timed stencil launches are bracketed (LIFE_TIMING_MODE, measurement
 // knob): 0 one event pair around a single-stream step call's launches (the
 // default: one hipEventRecord before the first launch, none between
 // launches), 1 per launch with hipEventRecord, 2 per launch stamped by the
 // dispatch itself (hipExtLaunchKernel), 3 no events.
 enum TimingMode { kTimeCall = 0, kTimeRecord = 1, kTimeExt = 2, kTimeOff = 3 };
-// LIFE_STREAM_PRIORITY (0/1, default 0): ring + comm streams at the greatest
-// HIP stream priority, the interior stream at the least (shard_alloc).
-// Measured off (profiles/r04/a): the RCCL-loopback halo stays 0.23 ms beside
-// the interior either way (86.5-91.2 T with, 90.0-90.8 T without), and the
-// LOCAL 4-shard strong line drops 48.9 -> 34.4 T (its device copies on the
-// high-priority stream slow the interior 0.148 -> 0.281 ms).
-static bool stream_priorities() {
-    static const bool v = [] {
-        const char *e = getenv("LIFE_STREAM_PRIORITY");
-        return e ? atoi(e) != 0 : false;
-    }();
-    return v;
-}
-static const int kEnvTimingMode = [] {
-    const char *e = getenv("LIFE_TIMING_MODE");
-    const int v = e ? atoi(e) : 0;
-    return v >= 0 && v <= 3 ? v : 0;
-}();
+static const int kEnvTimingMode = life::env::read(life::env::kTimingMode);
 
 struct life_dev {
     int64_t nx = 0, ny = 0;
@@ -243,24 +207,20 @@ life::Wrap wrap_of(const life_dev *d) { return life::Wrap{!part(d, 0) && !self_w
 // encoding, so a cell a kernel should have written but did not, or an apron
 // read before its halo arrived, changes the result on every run instead of
 // hiding behind a zeroed buffer that looks like a dead grid.
-int alloc_fill_byte() {
-    const char *e = getenv("LIFE_POISON");
-    return e && atoi(e) != 0 ? 0xA5 : 0;
-}
+int alloc_fill_byte() { return life::env::read(life::env::kPoison) ? 0xA5 : 0; }
 
 int shard_alloc(life_dev *d, Shard &s) {
     HIPCHK(hipSetDevice(s.device));
     // The streams first: every fill below is ordered on the stream that later
     // uses the buffer (the null stream does not order against non-blocking
     // streams), and finished before the shard is handed out.
-    // Priorities (LIFE_STREAM_PRIORITY=1, off by default): the comm and ring
-    // streams at the greatest priority, the interior at the least.
-    int prio_lo = 0, prio_hi = 0;
-    HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-    const bool prio = stream_priorities();
-    HIPCHK(hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, prio ? prio_hi : 0));
-    HIPCHK(hipStreamCreateWithPriority(&s.stream2, hipStreamNonBlocking, prio ? prio_lo : 0));
-    HIPCHK(hipStreamCreateWithPriority(&s.comm_stream, hipStreamNonBlocking, prio ? prio_hi : 0));
+    // All three at priority 0: the comm and ring streams at the greatest
+    // priority and the interior at the least kept the RCCL-loopback halo at
+    // 0.23 ms beside the interior (86.5-91.2 T with, 90.0-90.8 T without) and
+    // dropped the LOCAL 4-shard strong line 48.9 -> 34.4 T (profiles/r04/a).
+    HIPCHK(hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, 0));
+    HIPCHK(hipStreamCreateWithPriority(&s.stream2, hipStreamNonBlocking, 0));
+    HIPCHK(hipStreamCreateWithPriority(&s.comm_stream, hipStreamNonBlocking, 0));
     const int fill = alloc_fill_byte();
     const int64_t slack = s.lay.generations_per_exchange > 1 ? life::kTemporalSlackRows : 0;
     const size_t bytes = (size_t)(s.lay.pitch * (s.lay.rows + slack));
@@ -655,13 +615,7 @@ int launch_tiles(life_dev *d, Shard &s, const life::TileRegion *r, int nreg, int
 // behind the ring was exposed longer by as much (the half tiles take the
 // slots the RCCL kernels would get once the ring drains), so
 // the block did not get shorter.
-static bool interior_tail() {
-    static const bool v = [] {
-        const char *e = getenv("LIFE_INTERIOR_TAIL");
-        return e ? atoi(e) != 0 : false;
-    }();
-    return v;
-}
+static bool interior_tail() { static const bool v = life::env::read(life::env::kInteriorTail) != 0; return v; }
 
 // The overlapped schedule of one exchange block (round 5, profiles/r05/c-d
 // kernel traces): the ring tiles, then the halo of their new state (pack,
@@ -678,16 +632,6 @@ static bool interior_tail() {
 // +8 % on the halo side; 32768x65536 4.3 rounds +1.7 % on the interior's) --
 // else the interior's (`stream2` waits for the halo and the two handles are
 // swapped, so `stream` always names the one that carries on).
-// LIFE_JOIN (read once): 0 auto, 1 always the halo's stream, 2 always the
-// interior's.
-int join_mode() {
-    static const int v = [] {
-        const char *e = getenv("LIFE_JOIN");
-        const int m = e ? atoi(e) : 0;
-        return m >= 0 && m <= 2 ? m : 0;
-    }();
-    return v;
-}
 
 // Phase timing of one overlapped block (timing on): ring0 before the ring
 // kernels on the compute stream, ring1 after them, halo0 / halo1 around the
@@ -709,14 +653,13 @@ int phase_ring(Shard &s, PhaseEvents *pe) {
     }
     return LIFE_OK;
 }
-// halo_side[si]: shard si carries on in its halo's stream (see join_mode).
+// halo_side[si]: shard si carries on in its halo's stream (see carry_on_halo_side).
 int phase_end(life_dev *d, const std::vector<PhaseEvents *> &pe, const std::vector<char> &halo_side) {
     for (size_t si = 0; si < d->shards.size(); ++si) {
         Shard &s = d->shards[si];
         HIPCHK(hipSetDevice(s.device));
         if (pe[si]) HIPCHK(hipEventRecord(pe[si]->halo1, s.stream));
-        // (priorities belong to the stream roles: no swap then)
-        if (halo_side[si] || stream_priorities()) {
+        if (halo_side[si]) {
             HIPCHK(hipEventRecord(s.ev_int, s.stream2));
             HIPCHK(hipStreamWaitEvent(s.stream, s.ev_int, 0));
         } else {
@@ -728,11 +671,9 @@ int phase_end(life_dev *d, const std::vector<PhaseEvents *> &pe, const std::vect
     }
     return LIFE_OK;
 }
-// The auto rule of join_mode: ring + interior tiles under three rounds of
-// resident workgroups.
+// The rule above: ring + interior tiles under three rounds of resident
+// workgroups.
 bool carry_on_halo_side(int64_t block_items, int slots) {
-    const int m = join_mode();
-    if (m != 0) return m == 1;
     return slots > 0 && block_items < 3 * (int64_t)slots;
 }
 
@@ -916,8 +857,7 @@ int generation(life_dev *d) {
     }
     CHK(exchange(d, 1, false));  // halo of nxt, behind the ring on the compute streams
     // one-generation launches are short: carry on in the interior's stream
-    // unless LIFE_JOIN says otherwise
-    CHK(phase_end(d, pe, std::vector<char>(d->shards.size(), join_mode() == 1 ? 1 : 0)));
+    CHK(phase_end(d, pe, std::vector<char>(d->shards.size(), 0)));
     for (Shard &s : d->shards) s.cur ^= 1;
     return LIFE_OK;
 }
@@ -926,11 +866,7 @@ int generation(life_dev *d) {
 // (LIFE_COMM_TIMEOUT_S, default 600): a peer that died or never joined would
 // otherwise leave this rank spinning in an RCCL kernel forever.
 double comm_timeout_s() {
-    static const double t = [] {
-        const char *e = getenv("LIFE_COMM_TIMEOUT_S");
-        const double v = e ? atof(e) : 0.0;
-        return v > 0.0 ? v : 600.0;
-    }();
+    static const double t = life::env::read(life::env::kCommTimeoutS);
     return t;
 }
 

@@ -15,6 +15,7 @@
 #include <mutex>
 #include <vector>
 
+#include "life_env.h"
 #include "life_host.h"
 #include "life_mi355x.h"
 
@@ -67,15 +68,14 @@ int life_dims_choose(int64_t nx, int64_t ny, int n, int policy, int dims[2]) {
 // of a job must see the same values); 1 selects the one-generation layouts
 // (a measurement knob: the HBM-bound kernels).  The byte encoding moves 8x
 // the bytes per cell, so it amortises each HBM pass over more generations.
-static int env_depth(const char *name, int dflt) {
-    const char *e = getenv(name);
-    const int v = e ? atoi(e) : 0;
-    return v == 1 || v == 8 || v == 12 || v == 16 || v == 24 || v == 32 ? v : dflt;
+static int env_depth(const life::env::IntKnob &k) {
+    const int v = life::env::read(k);
+    return v == 1 || v == 8 || v == 12 || v == 16 || v == 24 || v == 32 ? v : k.dflt;
 }
 static int temporal_depth(int kernel) {
-    static const int kbit = env_depth("LIFE_TEMPORAL_DEPTH", LIFE_TEMPORAL_DEPTH);
+    static const int kbit = env_depth(life::env::kTemporalDepth);
     static const int kbyte = [] {  // the byte tiles are built for 16 or 32 ghost rows
-        const int v = env_depth("LIFE_TEMPORAL_DEPTH_BYTE", LIFE_TEMPORAL_DEPTH_BYTE);
+        const int v = env_depth(life::env::kTemporalDepthByte);
         return v == 1 || v == 16 ? v : 32;
     }();
     return kernel == LIFE_KERNEL_BIT ? kbit : kbyte;

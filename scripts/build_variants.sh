@@ -16,9 +16,10 @@ for spec in "$@"; do
     else
         git archive "$rev" mpi-and-open-mp_amd/csrc include | tar -x -C "$src"
     fi
-    (for f in life_kernels.hip life_dev.hip life_plan.cpp; do
+    (rm -f $d/*.o
+     for f in "$src"/mpi-and-open-mp_amd/csrc/*.hip "$src"/mpi-and-open-mp_amd/csrc/*.cpp; do
          /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 $defs -I"$src/include" \
-             -I"$src/mpi-and-open-mp_amd/csrc" -c "$src/mpi-and-open-mp_amd/csrc/$f" -o "$d/$f.o" &
+             -I"$src/mpi-and-open-mp_amd/csrc" -c "$f" -o "$d/$(basename "$f").o" &
      done; wait
      /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $d/liblife_mi355x.so $d/*.o \
          -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib && rm -rf "$src") &

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Sweep of the bit tile shape (pair rows R x waves NW) and the generations per
 pass m at 65536^2 (measurement tool): one bench.py process per point, since
-the knobs are read at library load (LIFE_TEMPORAL_ROWS, LIFE_TILE_WAVES,
-LIFE_BLOCK_GENS).  Writes one JSON line per run to the output file.
+the knobs are read at library load (LIFE_TEMPORAL_ROWS, LIFE_BLOCK_GENS).
+Only shapes with a kernel instance run (8 waves; LIFE_BIT_SHAPES in
+life_kernels.hip).  Writes one JSON line per run to the output file.
 
-  python3 scripts/shape_sweep.py OUT.jsonl [--shapes 24x8,16x16] [--m 10,20] [--modes default,driver]
+  python3 scripts/shape_sweep.py OUT.jsonl [--shapes 24x8,16x8] [--m 10,20] [--modes default,driver]
 """
 import argparse
 import json
@@ -20,7 +21,7 @@ MODES = {"default": [], "driver": ["--steps", "20", "--warmup", "5"]}
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("out")
-    p.add_argument("--shapes", default="24x8,16x8,32x8,24x12,16x16,24x16")
+    p.add_argument("--shapes", default="24x8,16x8")
     p.add_argument("--m", default="10,12,16,20")
     p.add_argument("--modes", default="default,driver")
     p.add_argument("--size", default="65536")
@@ -32,7 +33,7 @@ def main():
             R, NW = shape.split("x")
             for m in a.m.split(","):
                 for mode in [md for md in a.modes.split(",") for _ in range(a.reps)]:
-                    env = dict(os.environ, LIFE_TEMPORAL_ROWS=R, LIFE_TILE_WAVES=NW, LIFE_BLOCK_GENS=m)
+                    env = dict(os.environ, LIFE_TEMPORAL_ROWS=R, LIFE_BLOCK_GENS=m)
                     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--size", a.size,
                            *MODES[mode], *a.extra.split()]
                     t = time.time()

@@ -66,7 +66,9 @@ with lm.Life(a.size, a.size, kernel=a.kernel) as life:
         "live_count_frac_of_copy_ceiling": round(nbytes / (c * 1e-3) / 1e9 / copy, 4),
         "gather_density_frac_of_copy_ceiling": round(nbytes / (dm * 1e-3) / 1e9 / copy, 4),
         "set_cells_50_ms": round(statistics.median(set_ms), 4),
-        "gather_rect_512_ms": round(statistics.median(rect_ms), 4)})
+        "gather_rect_512_ms": round(statistics.median(rect_ms), 4),
+        "set_cells_50_ms_all": [round(v, 4) for v in set_ms],
+        "gather_rect_512_ms_all": [round(v, 4) for v in rect_ms]})
     print(line, flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
