@@ -60,7 +60,7 @@ constexpr FlagKnob kXcdOrder{"LIFE_XCD_ORDER", 1};
 constexpr FlagKnob kXcdOrderByte{"LIFE_XCD_ORDER_BYTE", 1};
 // launch-tail split: 0 none, 1 the round-4 rule, 2 the list-scheduling model (profiles/r06/c)
 constexpr IntKnob kTailSplit{"LIFE_TAIL_SPLIT", 2, 0, 2};
-// ---- device runtime (life_dev.hip)
+// ---- device runtime (life_dev.hip; LIFE_TIMING_MODE life_timing.hip, LIFE_INTERIOR_TAIL life_step.hip)
 // generations per pass for both encodings; 0 = per encoding: bit 12, byte 32 (profiles/r03/r4g, r4d)
 constexpr IntKnob kBlockGens{"LIFE_BLOCK_GENS", 0, 1, 32};
 // default of LIFE_OPT_FLOW: 0 off, 1 / 2 the dataflow forms, 3 automatic (profiles/r02/flow_ab.txt, r03/r4g)

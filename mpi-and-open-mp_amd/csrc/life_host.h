@@ -13,6 +13,42 @@ namespace life {
 int halo_plan(int64_t nx, int64_t ny, int dims0, int dims1, int rank, int kernel, int loop, life_halo_op *ops,
               int max_ops);
 
+#pragma GCC visibility push(hidden)  // the runtime's own: not among the library's dynamic symbols
+// The LOCAL transport's pairing of a halo plan's messages, and the staging
+// slots both transports use (pure: life_halo.hip resolves them once per plan).
+// halo_op_slot: staging slot of op i = earlier ops of its phase with the same
+// kind and what.
+int halo_op_slot(const life_halo_op *ops, int i);
+// halo_match_send: the send in `peer_ops` (the plan of rank mine[recv].peer)
+// that receive `recv` of rank `rank`'s plan `mine` copies from: within a
+// phase, the k-th receive from a peer pairs with the peer's k-th send to
+// `rank`.  Returns its index, -1 when there is none.
+int halo_match_send(const life_halo_op *mine, int recv, int rank, const life_halo_op *peer_ops, int npeer);
+// halo_wait_peers: the peers other than `rank` itself named by the ops of
+// `phase` and `kind`, each once, in plan order; returns their number (<= n).
+int halo_wait_peers(const life_halo_op *ops, int n, int rank, int phase, int kind, int *peers);
+
+// The next pass of a step call of the temporal tiles with `remaining` > 0
+// generations left: K generations per exchange, at most bmax per pass, `since`
+// generations advanced since the aprons were last filled (deep halo).  Every
+// rank must compute this identically, or their send / receive groups stop
+// pairing.
+//  * deep: the call is cut at the K boundary (K - since generations; 32 =
+//    11 + 11 + 10 at 12 generations per pass at most);
+//  * the segment is split into ceil(seg / bmax) passes of nearly equal size
+//    (a 20-generation call runs 10 + 10, not 16 + 4);
+//  * refill_first: the aprons no longer cover the pass (since + m > K: a
+//    longer pass than planned for, or the deep halo switched off while they
+//    were part-used) -- exchange before it, since' = 0;
+//  * extend: (deep) the aprons still hold the next pass's ghost cells, so
+//    this pass skips the exchange and also advances the `ext` apron rows the
+//    next one reads; not on the call's last pass (remaining == m) when the
+//    next call's first pass could not fit (since' + m + bmax > K);
+//  * otherwise the pass ends with the K-deep exchange.
+struct PassPlan { int m; bool refill_first; bool extend; int ext; };  // ext = K - since' - m, since' after the refill
+PassPlan next_pass(int K, int bmax, bool deep, int since, int64_t remaining);
+#pragma GCC visibility pop
+
 // The dataflow queue head is 32-bit: one launch may hold at most
 // kFlowMaxHead pulls (its items plus one extra pull per resident workgroup).
 // flow_chunk_passes: passes of `tiles` items each one launch of `grid`
@@ -27,7 +63,7 @@ int64_t flow_chunk_passes(int64_t tiles, int64_t grid, int64_t cap);
 // world-1) places its own block first, then receives the others in rank order
 // into two alternating staging slots (block k+1 arrives while block k is copied
 // out).  Pure arithmetic on life_layout_query, shared by the device gather
-// (life_dev.hip gather_impl) and the CPU tests.
+// (life_frames.hip gather_impl) and the CPU tests.
 enum GatherFormat { kGatherDense = 0, kGatherVtk = 1, kGatherBits = 2 };
 struct GatherPiece {
     int32_t rank;         // the block's global rank

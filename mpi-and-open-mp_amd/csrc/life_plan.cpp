@@ -148,6 +148,47 @@ int64_t life::flow_chunk_passes(int64_t tiles, int64_t grid, int64_t cap) {
     return cap > 0 && cap < n ? cap : n;
 }
 
+life::PassPlan life::next_pass(int K, int bmax, bool deep, int since, int64_t remaining) {
+    int64_t seg = remaining;
+    if (deep && since < K) seg = std::min(seg, (int64_t)(K - since));
+    const int64_t n = (seg + bmax - 1) / bmax;
+    PassPlan p;
+    p.m = (int)((seg + n - 1) / n);
+    p.refill_first = since + p.m > K;
+    if (p.refill_first) since = 0;
+    const bool last = remaining == p.m;
+    p.extend = deep && since + p.m < K && !(last && since + p.m + bmax > K);
+    p.ext = K - since - p.m;
+    return p;
+}
+
+int life::halo_op_slot(const life_halo_op *ops, int i) {
+    int n = 0;
+    for (int k = 0; k < i; k++) n += ops[k].phase == ops[i].phase && ops[k].kind == ops[i].kind && ops[k].what == ops[i].what;
+    return n;
+}
+
+int life::halo_match_send(const life_halo_op *mine, int recv, int rank, const life_halo_op *peer_ops, int npeer) {
+    const life_halo_op &o = mine[recv];
+    int kth = 0;  // this is the kth recv from o.peer in its phase
+    for (int k = 0; k < recv; k++)
+        kth += mine[k].phase == o.phase && mine[k].kind == LIFE_HALO_RECV && mine[k].peer == o.peer;
+    for (int k = 0; k < npeer; k++) {
+        const life_halo_op &q = peer_ops[k];
+        if (q.phase == o.phase && q.kind == LIFE_HALO_SEND && q.peer == rank && kth-- == 0) return k;
+    }
+    return -1;
+}
+
+int life::halo_wait_peers(const life_halo_op *ops, int n, int rank, int phase, int kind, int *peers) {
+    int ns = 0;
+    for (int i = 0; i < n; i++) {
+        if (ops[i].phase != phase || ops[i].kind != kind || ops[i].peer == rank) continue;
+        if (std::find(peers, peers + ns, ops[i].peer) == peers + ns) peers[ns++] = ops[i].peer;
+    }
+    return ns;
+}
+
 int64_t life::gather_frame_row_bytes(int64_t nx, int fmt) {
     return fmt == kGatherBits ? (nx + 7) / 8 : nx * (fmt == kGatherVtk ? 2 : 1);
 }

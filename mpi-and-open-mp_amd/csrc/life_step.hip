@@ -1,0 +1,606 @@
+// life_step.hip -- life_dev_step: the schedule of a step call.  Per generation
+// (life_cart.c:73-74):
+//   life_step     -> stencil kernel(s) cur -> nxt            (life_kernels.hip)
+//   life_exchange -> the halo of the new state               (life_halo.hip)
+// Overlap: the stencil is split into the boundary ring and the interior; the
+// ring runs first, the halo exchange of the NEW state runs behind it while
+// the interior kernel runs on the second compute stream.  Which passes a
+// call runs, and which of them exchange, is life::next_pass (life_plan.cpp).
+#include <chrono>
+#include <utility>
+
+#include "life_dev_internal.h"
+#include "life_env.h"
+
+using namespace life::rt;
+
+// LIFE_OPT_FLOW 3 takes the dataflow form when a pass holds fewer rounds of
+// resident workgroups (flow_form).
+constexpr double kFlowAutoRounds = 5.0;
+// fewest passes a call runs in the dataflow form
+constexpr int64_t kFlowMinPasses = 4;
+
+namespace {
+
+// Launches one stencil region on `st`; when timing is on and `timed`,
+// brackets it with HIP events on that stream and books its algorithmic bytes
+// (1 B read + 1 B written per BYTE cell, 2 bits per BIT cell).
+int launch_region(life_dev *d, Shard &s, const life::Region &r, bool timed, hipStream_t st) {
+    Bracket b;
+    CHK(bracket_begin(d, s, timed, 1, kExtNever, false, st, &b));
+    HIPCHK(life::launch_step(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], s.sink, r, wrap_of(d), st));
+    CHK(bracket_end(b, st));
+    if (b.t) {  // (no timer counts it -- span-only timing, LIFE_TIMING_MODE=3: no booking)
+        const bool bit = s.lay.kernel == LIFE_KERNEL_BIT;
+        const int64_t cpu = bit ? 128 : 16;
+        const int64_t xa = r.u0 * cpu, xb = r.u1 * cpu < s.lay.w ? r.u1 * cpu : s.lay.w;
+        book(d, bit, (double)(xb - xa) * (double)(r.r1 - r.r0), 1.0, 1.0, 0.0);
+    }
+    return LIFE_OK;
+}
+
+// Launches up to 4 tile regions of the temporal stencil as ONE kernel on
+// `st` (m generations, cur -> nxt), optionally timed.
+int launch_tiles(life_dev *d, Shard &s, const life::TileRegion *r, int nreg, int m, bool timed, hipStream_t st,
+                 life::Extend xt = life::Extend{}, int64_t concurrent = 0) {
+    // events stamped by the dispatch itself: no event packets between the
+    // launches of a multi-stream step (kTimeCall's one pair per call is for
+    // single-stream calls)
+    Bracket b;
+    CHK(bracket_begin(d, s, timed, 1, kExtModeExt | kExtModeCall, false, st, &b));
+    double valu = 0.0;
+    HIPCHK(life::launch_tstep(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], r, nreg, m, wrap_of(d), st, &valu, b.ext_a,
+                              b.ext_b, xt, concurrent));
+    CHK(bracket_end(b, st));
+    if (b.t) {  // (no timer counts it -- span-only timing, LIFE_TIMING_MODE=3: no booking)
+        const life::TileGeom g = life::tile_geom(life::extended_layout(s.lay, xt), m);
+        double cells = 0.0;
+        for (int k = 0; k < nreg; k++) {
+            // owned cells only (a deep-halo pass's apron rows are not counted)
+            const int64_t xa = r[k].tx0 * g.lanes * g.cells, xb = std::min(r[k].tx1 * g.lanes * g.cells, s.lay.w);
+            const int64_t ya = std::max(r[k].ty0 * g.rows - xt.y, (int64_t)0),
+                          yb = std::min(r[k].ty1 * g.rows - xt.y, s.lay.h);
+            if (xb > xa && yb > ya) cells += (double)(xb - xa) * (double)(yb - ya);
+        }
+        // valu as tiled: tiles, banded items, half-height tail tiles
+        book(d, s.lay.kernel == LIFE_KERNEL_BIT, cells, (double)m, 1.0, valu);
+    }
+    return LIFE_OK;
+}
+
+// LIFE_INTERIOR_TAIL (0/1, default 0, read once; A/B knob): 1 = the
+// exchange pass's interior launch takes the banded half-height tail, planned
+// with the ring's tiles counted as holding their slots; 0 = as in round 5,
+// only a full-width interior (a row strip's) splits, planned alone.  Off by default: in
+// r06f's ABAB loopback lines it shortened the interior by 4-9 % but the halo
+// behind the ring was exposed longer by as much (the half tiles take the
+// slots the RCCL kernels would get once the ring drains), so
+// the block did not get shorter.
+bool interior_tail() { static const bool v = life::env::read(life::env::kInteriorTail) != 0; return v; }
+
+// The overlapped schedule of one exchange block (round 5, profiles/r05/c-d
+// kernel traces): the ring tiles, then the halo of their new state (pack,
+// RCCL / copies, unpack) on the compute stream `stream`, back to back in one
+// hardware queue; the interior tiles concurrently on `stream2`.  The block
+// ends with ONE cross-queue wait, placed on the stream whose work is
+// predicted to end first: a queue that reaches a wait whose event has
+// already fired passes it at once, while one that must sleep on it woke
+// ~20 us after the event on MI355X (the halo's end to the next pass, r05d).
+// So the work carries on in the queue predicted to finish last: the halo's
+// (`stream`, which then waits for the interior) when the block is under
+// three rounds of tiles -- small shards, where ring + halo outlast the
+// interior (RCCL loopback, r05e: 16384x32768 1.1 rounds, 32768^2 2.2 rounds
+// +8 % on the halo side; 32768x65536 4.3 rounds +1.7 % on the interior's) --
+// else the interior's (`stream2` waits for the halo and the two handles are
+// swapped, so `stream` always names the one that carries on).
+
+// Phase timing of one overlapped block (timing on): ring0 before the ring
+// kernels on the compute stream, ring1 after them, halo0 / halo1 around the
+// halo on the same stream; the interior kernel is bracketed on the second
+// compute stream; `end` after the join on the stream that carries on.
+int phase_begin(life_dev *d, Shard &s, PhaseEvents **pe) {
+    *pe = nullptr;
+    if (!d->timing || !d->phase_events) return LIFE_OK;
+    int rc;
+    *pe = phase_slot(s, &rc);
+    if (!*pe) return rc;
+    HIPCHK(hipEventRecord((*pe)->ring0, s.stream));
+    return LIFE_OK;
+}
+int phase_ring(Shard &s, PhaseEvents *pe) {
+    if (pe) {
+        HIPCHK(hipEventRecord(pe->ring1, s.stream));
+        HIPCHK(hipEventRecord(pe->halo0, s.stream));
+    }
+    return LIFE_OK;
+}
+// halo_side[si]: shard si carries on in its halo's stream (see carry_on_halo_side).
+int phase_end(life_dev *d, const std::vector<PhaseEvents *> &pe, const std::vector<char> &halo_side) {
+    for (size_t si = 0; si < d->shards.size(); ++si) {
+        Shard &s = d->shards[si];
+        HIPCHK(hipSetDevice(s.device));
+        if (pe[si]) HIPCHK(hipEventRecord(pe[si]->halo1, s.stream));
+        if (halo_side[si]) {
+            HIPCHK(hipEventRecord(s.ev_int, s.stream2));
+            HIPCHK(hipStreamWaitEvent(s.stream, s.ev_int, 0));
+        } else {
+            HIPCHK(hipEventRecord(s.ev_halo, s.stream));
+            HIPCHK(hipStreamWaitEvent(s.stream2, s.ev_halo, 0));
+            std::swap(s.stream, s.stream2);
+        }
+        if (pe[si]) HIPCHK(hipEventRecord(pe[si]->end, s.stream));
+    }
+    return LIFE_OK;
+}
+// The rule above: ring + interior tiles under three rounds of resident
+// workgroups.
+bool carry_on_halo_side(int64_t block_items, int slots) {
+    return slots > 0 && block_items < 3 * (int64_t)slots;
+}
+
+// One block without overlap: `all(s)` launches every cell of shard s on its
+// compute stream; then the buffers flip and, when `halo`, the new state's
+// halo is exchanged on the compute streams, after the launch.
+template <class All>
+int whole_block(life_dev *d, bool halo, All all) {
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        CHK(all(s));
+    }
+    for (Shard &s : d->shards) s.cur ^= 1;
+    return halo ? exchange(d, 0, false) : LIFE_OK;
+}
+
+// One overlapped block (the schedule above).  ring(s) launches the boundary
+// ring of shard s on s.stream (untimed: the phase events cover it);
+// interior(s, &halo_side) launches the interior on s.stream2 and may choose
+// to carry on in the halo's stream (default: the interior's).
+template <class Ring, class Interior>
+int overlapped_block(life_dev *d, Ring ring, Interior interior) {
+    std::vector<PhaseEvents *> pe(d->shards.size(), nullptr);
+    std::vector<char> halo_side(d->shards.size(), 0);
+    for (size_t si = 0; si < d->shards.size(); ++si) {
+        Shard &s = d->shards[si];
+        HIPCHK(hipSetDevice(s.device));
+        // The interior (second stream) starts after everything on the compute
+        // stream: phase_end joined the previous block into ONE stream
+        // only (and may have swapped the handles), so without this fence the
+        // next interior could start beside the previous interior (still
+        // reading cur) or beside the previous ring + halo; a
+        // deep-halo pass before this one is not joined into the other
+        // streams either.
+        HIPCHK(hipEventRecord(s.ev_entry, s.stream));
+        HIPCHK(hipStreamWaitEvent(s.stream2, s.ev_entry, 0));
+        CHK(phase_begin(d, s, &pe[si]));
+        CHK(ring(s));
+        CHK(phase_ring(s, pe[si]));
+        if (pe[si]) HIPCHK(hipEventRecord(pe[si]->int0, s.stream2));
+        CHK(interior(s, &halo_side[si]));
+        if (pe[si]) HIPCHK(hipEventRecord(pe[si]->int1, s.stream2));
+    }
+    CHK(exchange(d, 1, false));  // halo of nxt, behind the ring on the compute streams
+    CHK(phase_end(d, pe, halo_side));
+    for (Shard &s : d->shards) s.cur ^= 1;
+    return LIFE_OK;
+}
+
+// One pass (life::next_pass) of the temporally blocked stencil on every
+// shard: m <= K generations, then one K-deep halo exchange.  Partitioned
+// shards: the boundary ring (one multi-region launch) runs on the compute
+// stream, the exchange of its new state behind it, and the interior
+// concurrently on the second compute stream.  The ring holds every tile that
+// produces a cell the exchange sends: rows [0, K) and [h-K, h), columns
+// [0, xa) and [w-xa, w) (xa = the x-apron, one lane column).  A self-wrapped
+// x axis (life::self_wrap_x) counts as partitioned: its "exchange" is the
+// column copy.
+int generation_block(life_dev *d, const life::PassPlan &p) {
+    const bool rx = part(d, 0) || self_wrap_x(d), ry = part(d, 1);
+    const int m = p.m;
+    // Deep halo (bit tiles, partitioned axes, no self-wrapped x): the
+    // exchange of a K-deep halo is skipped while the aprons still hold the
+    // next pass's ghost cells -- this pass then also advances the apron cells
+    // the next one reads (life::Extend) -- and runs after the pass whose
+    // successor would outrun them.  A 20-generation call of two 10-generation
+    // passes exchanges once instead of twice (life_cart.c:73-74 exchanges
+    // every generation).
+    // next_pass cuts a call into passes that end on the K boundary, so the
+    // exchange runs (overlapped with this pass) when the aprons are used up,
+    // or at the call's end when the next call's first pass could not fit.
+    if (p.refill_first) CHK(exchange(d, 0, false));
+    if (p.extend) {
+        life::Extend xt;
+        xt.y = ry ? p.ext : 0;
+        xt.x = part(d, 0);
+        CHK(whole_block(d, false, [&](Shard &s) -> int {
+            const life::TileGeom g = life::tile_geom(life::extended_layout(s.lay, xt), m);
+            const life::TileRegion all{0, g.ntx, 0, g.nty};
+            return launch_tiles(d, s, &all, 1, m, true, s.stream, xt);
+        }));
+        d->since += m;
+        return LIFE_OK;
+    }
+    if (!(rx || ry) || !d->overlap)
+        // one launch of every tile; a partitioned shard without overlap
+        // (LIFE_OPT_OVERLAP 0) then exchanges its halo on the compute
+        // stream, after the launch
+        return whole_block(d, rx || ry, [&](Shard &s) -> int {
+            const life::TileGeom g = life::tile_geom(s.lay, m);
+            const life::TileRegion all{0, g.ntx, 0, g.nty};
+            return launch_tiles(d, s, &all, 1, m, true, s.stream);
+        });
+    // per shard: the ring's regions (ring) and the interior, set by the ring
+    // callable for the interior one that follows it
+    life::TileGeom g;
+    life::TileRegion ring[4], inner;
+    int n = 0;
+    return overlapped_block(
+        d,
+        [&](Shard &s) -> int {
+            const int64_t K = s.lay.generations_per_exchange;
+            // grid of tiles: NX x NY, tile height uh; tile columns [0, ca) and
+            // [cb, NX) hold the x-ring
+            g = life::tile_geom(s.lay, m);
+            const int64_t NX = g.ntx, NY = g.nty, uh = g.rows;
+            int64_t ca = 0, cb = NX;
+            if (rx) {  // the x-ring: tile columns holding cells [0, xa) and [w - xa, w)
+                ca = 1;
+                cb = std::max(std::min(((s.lay.w - s.lay.xapron) / g.cells) / g.lanes, NX), ca);
+            }
+            // unit rows [0, ra) and [rb, NY), unit columns [0, ca) and [cb, NX)
+            int64_t ra = 0, rb = NY;
+            if (ry) {
+                ra = std::min((K + uh - 1) / uh, NY);
+                rb = std::max(std::min((s.lay.h - K) / uh, NY), ra);
+            }
+            n = 0;
+            if (ra > 0) ring[n++] = life::TileRegion{0, NX, 0, ra};
+            if (rb < NY) ring[n++] = life::TileRegion{0, NX, rb, NY};
+            if (rb > ra) {
+                if (ca > 0) ring[n++] = life::TileRegion{0, ca, ra, rb};
+                if (cb < NX) ring[n++] = life::TileRegion{cb, NX, ra, rb};
+            }
+            inner = life::TileRegion{ca, cb, ra, rb};
+            return launch_tiles(d, s, ring, n, m, false, s.stream);
+        },
+        [&](Shard &s, char *halo_side) -> int {
+            int64_t ring_items = 0;
+            for (int k = 0; k < n; k++) ring_items += life::region_items(g, ring[k]);
+            const int64_t items = life::region_items(g, inner) + ring_items;
+            *halo_side = carry_on_halo_side(items, life::tile_slots(s.lay)) ? 1 : 0;
+            // LIFE_INTERIOR_TAIL=1: the interior's launch-tail plan counts the
+            // ring's tiles, dispatched just before it, as holding their slots
+            // (16384 x 32768's 584 interior tiles beside 249 ring tiles are one
+            // round plus a tail); default: only a row strip's full-width interior
+            // splits its tail, planned alone (round 5)
+            const int64_t conc = interior_tail() ? ring_items : (inner.tx0 == 0 && inner.tx1 == g.ntx ? 0 : -1);
+            if (inner.ty1 > inner.ty0 && inner.tx1 > inner.tx0)
+                return launch_tiles(d, s, &inner, 1, m, true, s.stream2, life::Extend{}, conc);
+            return LIFE_OK;
+        });
+}
+
+// One generation on every local shard (one-cell aprons).
+int generation(life_dev *d) {
+    const bool rx = part(d, 0), ry = part(d, 1);
+    if (!d->overlap || !(rx || ry))
+        return whole_block(d, true, [&](Shard &s) -> int {
+            return launch_region(d, s, life::Region{0, s.lay.units, 0, s.lay.h}, true, s.stream);
+        });
+    // Ring first (cells whose 3x3 neighbourhood reaches a partitioned axis'
+    // apron) on the compute stream, then the halo of the new state behind it;
+    // the interior runs concurrently on the second compute stream.
+    // One-generation launches are short: carry on in the interior's stream.
+    auto interior_rows = [&](const Shard &s, int64_t *ra, int64_t *rb) {
+        *ra = ry ? 1 : 0;
+        *rb = ry ? s.lay.h - 1 : s.lay.h;
+    };
+    return overlapped_block(
+        d,
+        [&](Shard &s) -> int {
+            const int64_t U = s.lay.units, H = s.lay.h;
+            int64_t ra, rb;
+            interior_rows(s, &ra, &rb);
+            if (ry) {
+                CHK(launch_region(d, s, life::Region{0, U, 0, 1}, false, s.stream));
+                if (H > 1) CHK(launch_region(d, s, life::Region{0, U, H - 1, H}, false, s.stream));
+            }
+            if (rx && rb > ra) {
+                CHK(launch_region(d, s, life::Region{0, 1, ra, rb}, false, s.stream));
+                if (U > 1) CHK(launch_region(d, s, life::Region{U - 1, U, ra, rb}, false, s.stream));
+            }
+            return LIFE_OK;
+        },
+        [&](Shard &s, char *) -> int {
+            const int64_t U = s.lay.units;
+            int64_t ra, rb;
+            interior_rows(s, &ra, &rb);
+            const int64_t ua = rx ? 1 : 0, ub = rx ? U - 1 : U;
+            if (rb > ra && ub > ua) return launch_region(d, s, life::Region{ua, ub, ra, rb}, true, s.stream2);
+            return LIFE_OK;
+        });
+}
+
+// A single-shard grid small enough for one CU's LDS runs every generation of
+// the call in one resident-workgroup launch (life_kernels.hip, small_kernel).
+// Mode 1 (default) windows the VGPR kernel over several CUs when one
+// workgroup would need strips of 4 rows or more (p46gun_big 500^2: 10 rows,
+// 212 -> 632 Gcell/s windowed); mode 3 windows whenever the shape allows.
+life::RegWinPlan win_plan(const life_dev *d) {
+    const life_layout &L = d->shards[0].lay;
+    if (d->small_mode == 3 || (d->small_mode == 1 && life::reg_small_rows(L) >= 4))
+        return life::reg_win_plan(L, d->win_rows, d->win_halo);
+    return life::RegWinPlan{};
+}
+
+bool small_grid(const life_dev *d) {
+    if (d->world != 1 || d->shards.size() != 1 || d->small_mode == 0 || d->loop != 0) return false;
+    const life_layout &L = d->shards[0].lay;
+    if (win_plan(d).blocks > 0) return true;
+    return (d->small_mode != 2 && life::reg_small_rows(L) > 0) ||
+           life::small_lds_bytes(L) <= life::kSmallMaxLds;
+}
+
+int step_small(life_dev *d, int64_t generations) {
+    Shard &s = d->shards[0];
+    HIPCHK(hipSetDevice(s.device));
+    // ONE event pair around the call's launches: events between the
+    // windowed kernel's ~9 us launches measured 45 % slower (gaps)
+    Bracket b;
+    CHK(bracket_begin(d, s, true, 1, kExtNever, true, s.stream, &b));
+    const life::RegWinPlan wp = win_plan(d);
+    int launches = 1;
+    if (wp.blocks > 0) {
+        // K generations per launch, buffers swapped per launch; between the
+        // launches of the call the grid stays in natural 32-cell words
+        launches = 0;
+        for (int64_t g = 0; g < generations; g += wp.K, ++launches) {
+            const int m = (int)(generations - g < wp.K ? generations - g : wp.K);
+            HIPCHK(life::launch_reg_win(s.lay, wp, s.buf[s.cur], s.buf[s.cur ^ 1], m, s.stream, g > 0,
+                                        g + m < generations));
+            s.cur ^= 1;
+        }
+    } else {
+        if (d->small_mode != 2 && life::reg_small_rows(s.lay) > 0)
+            HIPCHK(life::launch_reg_small(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], generations, s.stream));
+        else
+            HIPCHK(life::launch_small(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], generations, s.stream));
+        s.cur ^= 1;
+    }
+    CHK(bracket_end(b, s.stream));
+    if (b.t) {
+        b.t->launches = launches;  // stats: mean per launch
+        // CU-resident: HBM sees one import and one export of the grid per launch
+        book(d, s.lay.kernel == LIFE_KERNEL_BIT, (double)s.lay.w * (double)s.lay.h, (double)generations,
+             (double)launches, 0.0);
+    }
+    return LIFE_OK;
+}
+
+// The dataflow form a single-shard bit device runs its passes of m
+// generations in (1 / 2, the hand-off forms), or 0 (per-launch tiles).
+int flow_form(const life_dev *d, int *m_out) {
+    if (!d->flow || d->shards.size() != 1 || d->world != 1 || part(d, 0) || part(d, 1) || self_wrap_x(d) ||
+        d->kernel != LIFE_KERNEL_BIT)
+        return 0;
+    const life_layout &L = d->shards[0].lay;
+    const int m = max_pass_gens(d);
+    *m_out = m;
+    if (!life::flow_ok(L, m)) return 0;
+    // automatic: the dataflow form (write-through hand-off) when a pass is
+    // under kFlowAutoRounds rounds of resident workgroups -- 32768^2 (2.2
+    // rounds of 768) +8 %, 32768 x 65536 (4.3) +1 %, 65536^2 (8.6) -3 %
+    // (profiles/r05/a) -- except a pass of 1 to 1.5 rounds: it runs as one
+    // full round plus the banded half-height tail (launch_tstep), its tiles
+    // all finish together and the dataflow form has nothing to pipeline
+    // (16384 x 32768, 833 tiles on 768 slots: per-launch tiles 83.2-83.8 T
+    // against 73.7-75.2 T, profiles/r06/d; under one round the dataflow
+    // form overlaps the passes in the idle slots)
+    if (d->flow == 3) {
+        const double rounds = (double)life::flow_items_per_pass(L, m) / (double)std::max(life::flow_slots(L), 1);
+        return rounds < kFlowAutoRounds && !(rounds >= 1.0 && rounds < 1.5) ? 1 : 0;
+    }
+    return d->flow;
+}
+
+// Grows the shard's dataflow scratch (queue head, error word, per-tile pass
+// counts) to the tile grid of m generations per pass.
+int flow_scratch(Shard &s, int m) {
+    const life::TileGeom g = life::tile_geom(s.lay, m);
+    const size_t words = (size_t)(2 + g.ntx * g.nty);
+    if (words <= s.flow_words) return LIFE_OK;
+    if (s.flow) (void)hipFree(s.flow);
+    s.flow = nullptr;
+    s.flow_words = 0;
+    if (hipSetDevice(s.device) != hipSuccess || hipMalloc(&s.flow, words * sizeof(unsigned int)) != hipSuccess ||
+        hipMemsetAsync(s.flow, 0, 2 * sizeof(unsigned int), s.stream) != hipSuccess) {
+        set_err("dataflow scratch (%zu words)", words);
+        return LIFE_ENOMEM;
+    }
+    s.flow_words = words;
+    return LIFE_OK;
+}
+
+// Whole passes of the dataflow tiles (life::launch_tflow) for a step call of
+// `generations` on a single shard whose axes both wrap in the stencil;
+// *done = the generations it queued (a multiple of the pass size m), 0 when
+// the call takes the per-launch path.
+int step_flow(life_dev *d, int64_t generations, int64_t *done) {
+    *done = 0;
+    int m = 0;
+    const int form = flow_form(d, &m);
+    if (form == 0) return LIFE_OK;
+    Shard &s = d->shards[0];
+    const life_layout &L = s.lay;
+    const int64_t passes = generations / m;
+    // a call of 2-3 passes ran 0.58 ms per 10-generation pass against 0.42 for
+    // the per-launch tiles (profiles/r03/r4d); the dataflow form pays from
+    // about 4 passes (0.474 ms per 12-generation pass in long runs)
+    if (passes < kFlowMinPasses) return LIFE_OK;
+    CHK(flow_scratch(s, m));
+    HIPCHK(hipSetDevice(s.device));
+    // The queue head is a 32-bit counter every resident workgroup bumps once
+    // past the last item: split the passes so that items + grid stays below
+    // 2^31 per launch (life::flow_chunk_passes), flipping the buffer parity
+    // per chunk.
+    const int64_t tiles = life::flow_items_per_pass(L, m);
+    const int64_t per = life::flow_chunk_passes(tiles, life::flow_slots(L), d->flow_chunk);
+    if (per < 1) return LIFE_OK;  // a grid too large for one pass per launch: per-launch tiles
+    for (int64_t left = passes; left > 0;) {
+        const int64_t n = std::min(left, per);
+        Bracket b;
+        CHK(bracket_begin(d, s, true, (int)n, kExtModeExt, false, s.stream, &b));  // stats: mean per pass
+        HIPCHK(life::launch_tflow(L, s.buf[s.cur], s.buf[s.cur ^ 1], m, n, s.flow, s.flow + 2, wrap_of(d),
+                                  form, s.stream, b.ext_a, b.ext_b));
+        CHK(bracket_end(b, s.stream));
+        // work is booked only beside a timer that counts the launch (as
+        // launch_tiles / launch_region: LIFE_TIMING_MODE=3 and span-only
+        // timing book nothing, so bytes / updates per launch stay consistent)
+        if (b.t)
+            book(d, true, (double)L.w * (double)L.h, (double)n * (double)m, (double)n,
+                 (double)n * (double)life::flow_items_per_pass(L, m, true) * 64.0 *
+                     life::tstep_valu_per_tile_lane(m, false));
+        if (n & 1) s.cur ^= 1;
+        left -= n;
+    }
+    s.flow_used = true;
+    *done = passes * m;
+    return LIFE_OK;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+void note_pass(life_dev *d, std::chrono::steady_clock::time_point t0) {
+    const double ms = ms_since(t0);
+    d->call_passes++;
+    if (ms > d->call_pass_max_ms) d->call_pass_max_ms = ms;
+}
+
+// The launches of one step call (life_dev_step after its entry fence).
+int step_body(life_dev *d, int64_t generations) {
+    if (small_grid(d)) {
+        d->last_path = LIFE_PATH_SMALL;
+        constexpr int64_t kChunk = 1 << 20;  // generations per resident launch
+        for (int64_t g = 0; g < generations; g += kChunk)
+            CHK(step_small(d, generations - g < kChunk ? generations - g : kChunk));
+        // the LDS kernel wraps inside the CU and leaves the buffer's aprons
+        // stale: refresh them (a self-wrapped x axis; no-op otherwise)
+        return exchange(d, 0, false);
+    }
+    if (temporal(d)) {
+        int64_t done = 0;
+        CHK(step_flow(d, generations, &done));
+        d->last_path = done > 0 ? LIFE_PATH_FLOW : LIFE_PATH_TILES;
+        const int K = d->shards[0].lay.generations_per_exchange;
+        for (int64_t g = done; g < generations;) {
+            const life::PassPlan p = life::next_pass(K, max_pass_gens(d), deep_halo(d), d->since, generations - g);
+            const auto t0 = std::chrono::steady_clock::now();
+            CHK(generation_block(d, p));
+            note_pass(d, t0);
+            g += p.m;
+        }
+        return LIFE_OK;
+    }
+    d->last_path = LIFE_PATH_ONEGEN;
+    for (int64_t g = 0; g < generations; g++) {
+        const auto t0 = std::chrono::steady_clock::now();
+        CHK(generation(d));
+        note_pass(d, t0);
+    }
+    return LIFE_OK;
+}
+
+int step_call(life_dev *d, int64_t generations) {
+    // Entry fence: the second compute stream and the comm stream start after
+    // everything already queued on the compute stream (an asynchronous
+    // fill_random and its halo fill, a small-grid launch, a gather's export),
+    // which the overlapped schedule would otherwise race.  A single shard
+    // with no partitioned or self-wrapped axis steps on the compute stream
+    // alone: no fence (4 runtime calls off a ~1 ms call's critical path).
+    const bool one_stream = d->shards.size() == 1 && !part(d, 0) && !part(d, 1) && !self_wrap_x(d);
+    for (Shard &s : d->shards) {
+        if (one_stream) break;
+        HIPCHK(hipSetDevice(s.device));
+        HIPCHK(hipEventRecord(s.ev_entry, s.stream));
+        HIPCHK(hipStreamWaitEvent(s.stream2, s.ev_entry, 0));
+        HIPCHK(hipStreamWaitEvent(s.comm_stream, s.ev_entry, 0));
+    }
+    // kTimeCall: one event pair around all launches of a single-stream call
+    if (d->timing && one_stream && timing_mode() == kTimeCall && !small_grid(d) && temporal(d)) {
+        Shard &s = d->shards[0];
+        int rc;
+        d->call_timer = timer_slot(s, &rc);
+        if (!d->call_timer) return rc;
+        d->call_timer->launches = 0;
+        HIPCHK(hipEventRecord(d->call_timer->a, s.stream));
+        rc = step_body(d, generations);
+        TimedLaunch *t = d->call_timer;
+        d->call_timer = nullptr;
+        if (rc != LIFE_OK) {
+            // drop the half-recorded pair (no event b): a later harvest
+            // would fail on it and hide this call's error
+            s.timers_used--;
+            return rc;
+        }
+        HIPCHK(hipEventRecord(t->b, s.stream));
+        s.span_a = t->a;  // the call's pair is its span
+        s.span_b = t->b;
+        d->call_spans = true;
+        return LIFE_OK;
+    }
+    if (!d->timing) return step_body(d, generations);
+    // timing on, any other call: one event at each end of the call on every
+    // shard's compute stream (the entry fence above orders the other streams
+    // after the first; every schedule joins them back into it at the end)
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        if (!s.own_a) HIPCHK(hipEventCreate(&s.own_a));
+        if (!s.own_b) HIPCHK(hipEventCreate(&s.own_b));
+        HIPCHK(hipEventRecord(s.own_a, s.stream));
+    }
+    CHK(step_body(d, generations));
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        HIPCHK(hipEventRecord(s.own_b, s.stream));
+        s.span_a = s.own_a;
+        s.span_b = s.own_b;
+    }
+    d->call_spans = true;
+    return LIFE_OK;
+}
+
+}  // namespace
+
+// At creation: the scratch and one empty launch of the dataflow instance the
+// device's first dataflow call will run, so that call does not pay the
+// kernel's first launch (~140 us before configs[2]'s dataflow launch inside
+// its timed call, profiles/r05/l trace_32768).
+int life::rt::flow_prewarm(life_dev *d) {
+    int m = 0;
+    const int form = flow_form(d, &m);
+    if (form == 0) return LIFE_OK;
+    Shard &s = d->shards[0];
+    CHK(flow_scratch(s, m));
+    HIPCHK(hipSetDevice(s.device));
+    HIPCHK(life::prewarm_tflow(s.lay, m, form, s.flow, s.stream));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    return LIFE_OK;
+}
+
+extern "C" {
+
+int life_dev_step(life_dev *d, int64_t generations) {
+    if (!d || generations < 0) return LIFE_EINVAL;
+    if (generations == 0) return LIFE_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    d->call_passes = 0;
+    d->call_pass_max_ms = 0.0;
+    d->call_spans = false;
+    const int rc = step_call(d, generations);
+    d->call_host_ms = ms_since(t0);
+    return rc;
+}
+
+int life_dev_last_path(life_dev *d) { return d ? d->last_path : LIFE_EINVAL; }
+
+}  // extern "C"

@@ -92,7 +92,7 @@ def test_flow_back_to_back_and_chunked(gpu, oracle):
 
 def test_flow_needs_four_passes(gpu, oracle):
     """2-3 passes run as per-launch tiles (the dataflow form's start-up cost
-    is not repaid, life_dev.hip kFlowMinPasses), 4 take the dataflow form."""
+    is not repaid, life_step.hip kFlowMinPasses), 4 take the dataflow form."""
     nx, ny = 2048, 700
     g = oracle.fill_random(nx, ny, seed=37, density=0.5)
     with gpu.Life(nx, ny, kernel="bit", small_grid=False, flow=1) as life:
