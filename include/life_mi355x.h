@@ -355,6 +355,21 @@ int life_dev_set_timing(life_dev *d, int on);
 /* Option 10 (LIFE_OPT_SKEW, time-skewed ghost-free tiles) was retired in
  * round 5: 8 % slower per launch on MI355X; it now fails
  * with LIFE_EINVAL like any unknown option. */
+/* LIFE_OPT_PIPELINE (default LIFE_PIPELINE from the environment, else 1):
+ * a step call of at least 2 per-launch tile passes on a single shard whose
+ * axes both wrap inside it cuts every pass into R row regions, one launch
+ * each, dealt alternately over the shard's two compute streams and ordered
+ * by events: a region of pass p + 1 waits only for the regions r - 1, r, r + 1
+ * of pass p, and the order rotates by one region per pass, so the first
+ * region of the next pass starts in the launch tail of this one instead of
+ * behind a drained chip.  0: off (one launch per pass); 1: automatic (R =
+ * 4, when a pass holds at least 4 rounds of resident workgroups and the call
+ * at least 4 passes: where measured to win); 3..16: that many
+ * regions whenever the tile grid allows (at least 2 tile rows per region).
+ * Either encoding; LIFE_OPT_FLOW decides first.  Passes timed one by one
+ * (life_dev_set_timing with LIFE_TIMING_MODE 1 / 2) run as one launch each.
+ * Same results; the statistics count one launch per pass either way. */
+#define LIFE_OPT_PIPELINE 11
 int life_dev_configure(life_dev *d, int option, int value);
 /* The kernel family that ran the bulk of the last life_dev_step call:
  * LIFE_PATH_ONEGEN (one generation per launch), _TILES (temporally blocked

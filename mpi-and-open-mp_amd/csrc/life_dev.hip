@@ -63,6 +63,12 @@ static const int kEnvFlow = life::env::read(life::env::kFlow);
 // LIFE_DEEP_HALO (0/1, default 1) sets LIFE_OPT_DEEP_HALO's default at load
 // time (life_step.hip generation_block).
 static const bool kEnvDeepHalo = life::env::read(life::env::kDeepHalo) != 0;
+// LIFE_PIPELINE (0, 1, 3..16) sets LIFE_OPT_PIPELINE's default at load time
+// (life_step.hip pipelined_pass); 2 is no value of the option
+static const int kEnvPipeline = [] {
+    const int v = life::env::read(life::env::kPipeline);
+    return v == 2 ? life::env::kPipeline.dflt : v;
+}();
 static int default_block_gens(int kernel) {
     return kEnvBlockGens ? kEnvBlockGens : (kernel == LIFE_KERNEL_BIT ? 12 : 32);
 }
@@ -103,6 +109,7 @@ int shard_alloc(Shard &s) {
     HIPCHK(hipEventCreateWithFlags(&s.ev_halo, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&s.ev_sync, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&s.ev_entry, hipEventDisableTiming));
+    for (hipEvent_t &e : s.ev_pipe) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     const size_t col_bytes = (size_t)life::column_stage_bytes(s.lay);
     HIPCHK(hipMalloc(&s.col_send, col_bytes));
     HIPCHK(hipMalloc(&s.col_recv, col_bytes));
@@ -133,6 +140,8 @@ void shard_free(Shard &s) {
     if (s.d_count) (void)hipFree(s.d_count);
     if (s.h_count) (void)hipHostFree(s.h_count);
     for (hipEvent_t e : {s.ev_halo, s.ev_sync, s.ev_int, s.ev_entry, s.own_a, s.own_b})
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : s.ev_pipe)
         if (e) (void)hipEventDestroy(e);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.stream2) (void)hipStreamDestroy(s.stream2);
@@ -186,6 +195,7 @@ life_dev *new_dev(int64_t nx, int64_t ny, int dims0, int dims1, int world, int k
     d->block_gens = default_block_gens(kernel);
     d->deep = kEnvDeepHalo;
     d->flow = kEnvFlow;
+    d->pipe = kEnvPipeline;
     return d;
 }
 
@@ -519,6 +529,10 @@ int life_dev_configure(life_dev *d, int option, int value) {
         // (ADVICE r5): the call is collective there and checks agreement.
         if (d->rank_mode && d->world > 1) CHK(agree_all_ranks(d, value, "LIFE_OPT_DEEP_HALO"));
         d->deep = value != 0;
+        return LIFE_OK;
+    case LIFE_OPT_PIPELINE:
+        if (value < 0 || value == 2 || value > life::kPipeMaxRegions) return LIFE_EINVAL;
+        d->pipe = value;
         return LIFE_OK;
     case LIFE_OPT_FLOW_CHUNK:
         if (value < 0) return LIFE_EINVAL;

@@ -49,6 +49,8 @@ void set_err(const char *fmt, ...);
         if (rc_ != LIFE_OK) return rc_; \
     } while (0)
 
+constexpr int kPipeRing = 2 * life::kPipeMaxRegions;
+
 struct TimedLaunch {
     hipEvent_t a = nullptr, b = nullptr;
     int launches = 1;  // kernel launches between a and b (back-to-back on one stream)
@@ -80,6 +82,9 @@ struct Shard {
     hipStream_t comm_stream = nullptr;
     hipEvent_t ev_halo = nullptr, ev_sync = nullptr, ev_int = nullptr;
     hipEvent_t ev_entry = nullptr;  // life_dev_step entry fence (see there)
+    // pipelined passes (life_step.hip): launch i records ev_pipe[i % kPipeRing]
+    // when a later launch waits for it, at most 2 R - 1 <= kPipeRing - 1 launches on
+    hipEvent_t ev_pipe[kPipeRing] = {};
     // device span of the last step call (timing on): own_a / own_b recorded at
     // the call's two ends, or the kTimeCall pair borrowed (span_a / span_b)
     hipEvent_t own_a = nullptr, own_b = nullptr, span_a = nullptr, span_b = nullptr;
@@ -132,6 +137,14 @@ struct life_dev {
     int flow = 0;  // LIFE_OPT_FLOW: single-shard bit tiles as one persistent dataflow launch per
                    // step call (1: write-through hand-off, 2: plain stores + release; 0 off; creation: LIFE_FLOW)
     int64_t flow_chunk = 0;  // LIFE_OPT_FLOW_CHUNK: passes per dataflow launch at most (0: automatic)
+    int pipe = 0;  // LIFE_OPT_PIPELINE: 0 off, 1 automatic, R >= 3 regions whenever a plan exists (creation: LIFE_PIPELINE)
+    // the current step call's pipelined passes (life_step.hip pipelined_pass): R = 0, none; the plan
+    // and the pass count of the current run of passes of m generations (a new m: a new run)
+    struct {
+        int R = 0, m = 0;
+        int64_t pass = 0;
+        life::PipePlan plan;
+    } pipe_call;
     life::rt::TimedLaunch *call_timer = nullptr;  // kTimeCall: the pair bracketing the current step call
     std::vector<life::rt::Shard> shards;
     double acc_ms = 0.0;

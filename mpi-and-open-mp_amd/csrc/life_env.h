@@ -67,6 +67,8 @@ constexpr IntKnob kBlockGens{"LIFE_BLOCK_GENS", 0, 1, 32};
 constexpr IntKnob kFlow{"LIFE_FLOW", 3, 0, 3};
 // default of LIFE_OPT_DEEP_HALO
 constexpr FlagKnob kDeepHalo{"LIFE_DEEP_HALO", 1};
+// default of LIFE_OPT_PIPELINE: 0 off, 1 automatic, 3..16 that many row regions per pass (profiles/pipeline)
+constexpr IntKnob kPipeline{"LIFE_PIPELINE", 1, 0, 16};
 // timed launches: 0 one event pair per call, 1 per launch, 2 stamped by the dispatch, 3 no events (read by tests)
 constexpr IntKnob kTimingMode{"LIFE_TIMING_MODE", 0, 0, 3};
 // 1: allocations filled with 0xA5 instead of zeros; read at every life_dev_create* (tests set it in-process)

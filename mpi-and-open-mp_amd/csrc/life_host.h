@@ -47,6 +47,42 @@ int halo_wait_peers(const life_halo_op *ops, int n, int rank, int phase, int kin
 //  * otherwise the pass ends with the K-deep exchange.
 struct PassPlan { int m; bool refill_first; bool extend; int ext; };  // ext = K - since' - m, since' after the refill
 PassPlan next_pass(int K, int bmax, bool deep, int since, int64_t remaining);
+
+// Pipelined passes of a single wrapped shard (LIFE_OPT_PIPELINE): a pass of
+// nty tile rows is cut into R regions of whole tile rows, each its own
+// launch, dealt over S streams, so that the first region of pass p + 1 may
+// start in the launch tail of the last region of pass p.
+//  * Regions: R contiguous groups of nearly equal size covering [0, nty),
+//    each at least 2 tile rows (a last tile row shorter than the ghost depth
+//    lets tile row 0's window reach two tile rows up: still the neighbouring
+//    region).  With a banded last tile column (B > 1 tile rows per banded
+//    item) the boundaries fall on multiples of B when every region can hold
+//    a whole band (nty / B >= R: `aligned`); else they ignore B, and a
+//    region's bands, which start at its first tile row, take a few more items.
+//  * Order: pass p launches region (p + j) % R at position j = 0 .. R - 1;
+//    launch i = p R + j runs on stream i % S.
+//  * Dependencies: launch (p, r) reads what pass p - 1 wrote in regions r - 1,
+//    r, r + 1 (cyclic) and overwrites the rows those same three launches
+//    read.  They sit at positions (j + dr + 1) % R of pass p - 1, dr = -1, 0,
+//    1: R + j - that position launches back.
+//  * wait[j][0 .. nwait[j]): the launches, as distances back from i, that the
+//    launch at position j of a pass p >= 1 waits for by event -- the required
+//    ones that neither stream order nor a wait of an earlier launch of its
+//    stream implies, worked out over passes 0 and 1 (later passes only know
+//    more).  R = 4, S = 2: one wait, 3 back, at j = 0 .. 2.  The launches of
+//    pass 0 depend on the fence before them only.  record[j]: some launch
+//    waits for the one at position j.
+// R == 0: no plan (R < 3, nty < 2 R, or more regions / streams than kPipeMax*).
+constexpr int kPipeMaxRegions = 16, kPipeMaxStreams = 4;
+struct PipePlan {
+    int R = 0, S = 0;
+    bool aligned = false;
+    int64_t ty[kPipeMaxRegions + 1] = {};  // region r = tile rows [ty[r], ty[r + 1])
+    int nwait[kPipeMaxRegions] = {};
+    int wait[kPipeMaxRegions][kPipeMaxStreams] = {};
+    bool record[kPipeMaxRegions] = {};
+};
+PipePlan pipe_plan(int64_t nty, int64_t B, int R, int S);
 #pragma GCC visibility pop
 
 // The dataflow queue head is 32-bit: one launch may hold at most

@@ -162,6 +162,42 @@ life::PassPlan life::next_pass(int K, int bmax, bool deep, int since, int64_t re
     return p;
 }
 
+life::PipePlan life::pipe_plan(int64_t nty, int64_t B, int R, int S) {
+    PipePlan p;
+    if (R < 3 || R > kPipeMaxRegions || S < 1 || S > kPipeMaxStreams || nty < 2 * (int64_t)R) return p;
+    p.R = R;
+    p.S = S;
+    // regions: whole bands when each region can hold one, else whole tile rows;
+    // the rows the unit does not divide go to the last region
+    p.aligned = B > 1 && nty / B >= R;
+    const int64_t unit = p.aligned ? B : 1, units = nty / unit;
+    p.ty[0] = 0;
+    for (int r = 0; r < R; r++) p.ty[r + 1] = p.ty[r] + unit * (units / R + (r < units % R ? 1 : 0));
+    p.ty[R] = nty;
+    // waits: passes 0 and 1 with a vector clock per launch -- know[i][s] = the
+    // latest launch of stream s known to have finished when launch i starts
+    int know[2 * kPipeMaxRegions][kPipeMaxStreams];
+    for (int i = 0; i < 2 * R; i++) {
+        int *k = know[i];
+        for (int s = 0; s < S; s++) k[s] = i >= S ? know[i - S][s] : -1;
+        if (i >= S) k[i % S] = i - S;  // stream order
+        if (i < R) continue;           // pass 0: the fence before it only
+        const int j = i - R;
+        int need[3];
+        for (int dr = -1; dr <= 1; dr++) need[dr + 1] = ((j + dr + 1) % R + R) % R;  // launch index in pass 0
+        std::sort(need, need + 3, [](int a, int b) { return a > b; });                // the latest first
+        for (int q : need) {
+            if (k[q % S] >= q) continue;
+            p.wait[j][p.nwait[j]++] = i - q;
+            for (int s = 0; s < S; s++) k[s] = std::max(k[s], know[q][s]);
+            k[q % S] = std::max(k[q % S], q);
+        }
+    }
+    for (int j = 0; j < R; j++)
+        for (int w = 0; w < p.nwait[j]; w++) p.record[((j - p.wait[j][w]) % R + R) % R] = true;
+    return p;
+}
+
 int life::halo_op_slot(const life_halo_op *ops, int i) {
     int n = 0;
     for (int k = 0; k < i; k++) n += ops[k].phase == ops[i].phase && ops[k].kind == ops[i].kind && ops[k].what == ops[i].what;

@@ -68,6 +68,93 @@ int launch_tiles(life_dev *d, Shard &s, const life::TileRegion *r, int nreg, int
     return LIFE_OK;
 }
 
+// ---- pipelined passes (LIFE_OPT_PIPELINE; the plan: life::pipe_plan)
+// A whole-grid launch per pass drains the chip at every pass boundary: its
+// last round leaves slots idle (the half-height tail shortens that, DESIGN.md
+// 5.6) and the next launch starts with every tile loading its window at once.
+// Here a pass is R launches of row regions, alternating between the shard's
+// two compute streams; a region of the next pass needs only its own and the
+// two neighbouring regions of this pass, and the launch order rotates by one
+// region per pass, so the next pass's first region fills the slots the last
+// region of this pass frees.  No launch splits its tail: each ends beside
+// the next one's start.  The very last launch of a call has nothing behind
+// it and stays whole as well: giving it the half-height tail measured within
+// the run-to-run spread at 2, 4 and 83 passes (profiles/pipeline, lasttail).
+//
+// The tile grid depends on the pass length m (tile height 8R - 2m), and a
+// call's passes may differ by one generation (life::next_pass): each run of
+// passes of equal m is pipelined on its own, with both streams joined and
+// the rotation restarted between two runs (a call has at most two).
+
+// LIFE_OPT_PIPELINE 1, either encoding: this many regions, when every region
+// holds at least kPipeAutoRounds rounds of resident workgroups and the call
+// at least kPipeAutoPasses passes (profiles/pipeline).
+// Measured at 65536^2 (bit 8.65 rounds per pass, byte 13.6) and 32768 x 65536
+// (bit, 4.3 rounds, dataflow form off); 3 regions lose 6-8 % (every launch
+// then waits for the whole pass before it, and no tail is split), 6 and 8
+// are level with 4; calls of 2 to 16 passes are within their run-to-run
+// spread either way (+-5 %), those of 31 and 83 passes ahead in every run.
+constexpr int kPipeAutoRegions = 4;
+constexpr double kPipeAutoRounds = 1.0;
+constexpr int64_t kPipeAutoPasses = 4;
+
+int64_t tile_bands(const life::TileGeom &g) { return g.gsh < 6 ? 64 >> g.gsh : 1; }
+
+// stream2 starts after everything queued on stream / stream after everything on stream2
+int fence_stream2(Shard &s) {
+    HIPCHK(hipEventRecord(s.ev_entry, s.stream));
+    HIPCHK(hipStreamWaitEvent(s.stream2, s.ev_entry, 0));
+    return LIFE_OK;
+}
+int join_stream2(Shard &s) {
+    HIPCHK(hipEventRecord(s.ev_int, s.stream2));
+    HIPCHK(hipStreamWaitEvent(s.stream, s.ev_int, 0));
+    return LIFE_OK;
+}
+
+// One pass of m generations of a pipelined call on the single shard s (cur ->
+// nxt; the caller flips).  Booked as ONE launch of the whole grid.
+int pipelined_pass(life_dev *d, Shard &s, int m) {
+    auto &pc = d->pipe_call;
+    const life::TileGeom g = life::tile_geom(s.lay, m);
+    if (pc.m != m) {  // a new run of equal passes
+        if (pc.m != 0) {
+            CHK(join_stream2(s));
+            CHK(fence_stream2(s));
+        }
+        pc.plan = life::pipe_plan(g.nty, tile_bands(g), pc.R, 2);
+        pc.m = m;
+        pc.pass = 0;
+    }
+    const life::PipePlan &P = pc.plan;
+    if (P.R == 0) {  // no plan for this tile grid: one launch, the other stream idle
+        const life::TileRegion all{0, g.ntx, 0, g.nty};
+        return launch_tiles(d, s, &all, 1, m, true, s.stream);
+    }
+    Bracket b;  // the call's pair, or none (pipe_regions: no pass of a pipelined call takes a pair of its own)
+    CHK(bracket_begin(d, s, true, 1, kExtNever, false, s.stream, &b));
+    hipStream_t st[2] = {s.stream, s.stream2};
+    double valu = 0.0;
+    for (int j = 0; j < P.R; j++) {
+        const int64_t i = pc.pass * P.R + j;
+        const int r = (int)((pc.pass + j) % P.R);
+        hipStream_t q = st[i % 2];
+        if (pc.pass > 0)
+            for (int w = 0; w < P.nwait[j]; w++)
+                HIPCHK(hipStreamWaitEvent(q, s.ev_pipe[(i - P.wait[j][w]) % kPipeRing], 0));
+        const life::TileRegion reg{0, g.ntx, P.ty[r], P.ty[r + 1]};
+        double v = 0.0;
+        HIPCHK(life::launch_tstep(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], &reg, 1, m, wrap_of(d), q, &v, nullptr,
+                                  nullptr, life::Extend{}, -1));
+        valu += v;
+        if (P.record[j]) HIPCHK(hipEventRecord(s.ev_pipe[i % kPipeRing], q));
+    }
+    CHK(bracket_end(b, s.stream));
+    if (b.t) book(d, s.lay.kernel == LIFE_KERNEL_BIT, (double)s.lay.w * (double)s.lay.h, (double)m, 1.0, valu);
+    pc.pass++;
+    return LIFE_OK;
+}
+
 // LIFE_INTERIOR_TAIL (0/1, default 0, read once; A/B knob): 1 = the
 // exchange pass's interior launch takes the banded half-height tail, planned
 // with the ring's tiles counted as holding their slots; 0 = as in round 5,
@@ -224,6 +311,7 @@ int generation_block(life_dev *d, const life::PassPlan &p) {
         // (LIFE_OPT_OVERLAP 0) then exchanges its halo on the compute
         // stream, after the launch
         return whole_block(d, rx || ry, [&](Shard &s) -> int {
+            if (d->pipe_call.R > 0) return pipelined_pass(d, s, m);
             const life::TileGeom g = life::tile_geom(s.lay, m);
             const life::TileRegion all{0, g.ntx, 0, g.nty};
             return launch_tiles(d, s, &all, 1, m, true, s.stream);
@@ -420,31 +508,40 @@ int flow_scratch(Shard &s, int m) {
     return LIFE_OK;
 }
 
+// The whole passes of a step call of `generations` the dataflow form takes
+// (0: none, the call runs per-launch tiles), in form *form, of *m generations
+// each, at most *per of them per launch.
+int64_t flow_passes(const life_dev *d, int64_t generations, int *form, int *m, int64_t *per) {
+    *form = flow_form(d, m);
+    if (*form == 0) return 0;
+    const life_layout &L = d->shards[0].lay;
+    const int64_t passes = generations / *m;
+    // a call of 2-3 passes ran 0.58 ms per 10-generation pass against 0.42 for
+    // the per-launch tiles (profiles/r03/r4d); the dataflow form pays from
+    // about 4 passes (0.474 ms per 12-generation pass in long runs)
+    if (passes < kFlowMinPasses) return 0;
+    // The queue head is a 32-bit counter every resident workgroup bumps once
+    // past the last item: split the passes so that items + grid stays below
+    // 2^31 per launch (life::flow_chunk_passes), flipping the buffer parity
+    // per chunk.
+    *per = life::flow_chunk_passes(life::flow_items_per_pass(L, *m), life::flow_slots(L), d->flow_chunk);
+    return *per < 1 ? 0 : passes;  // a grid too large for one pass per launch: per-launch tiles
+}
+
 // Whole passes of the dataflow tiles (life::launch_tflow) for a step call of
 // `generations` on a single shard whose axes both wrap in the stencil;
 // *done = the generations it queued (a multiple of the pass size m), 0 when
 // the call takes the per-launch path.
 int step_flow(life_dev *d, int64_t generations, int64_t *done) {
     *done = 0;
-    int m = 0;
-    const int form = flow_form(d, &m);
-    if (form == 0) return LIFE_OK;
+    int m = 0, form = 0;
+    int64_t per = 0;
+    const int64_t passes = flow_passes(d, generations, &form, &m, &per);
+    if (passes == 0) return LIFE_OK;
     Shard &s = d->shards[0];
     const life_layout &L = s.lay;
-    const int64_t passes = generations / m;
-    // a call of 2-3 passes ran 0.58 ms per 10-generation pass against 0.42 for
-    // the per-launch tiles (profiles/r03/r4d); the dataflow form pays from
-    // about 4 passes (0.474 ms per 12-generation pass in long runs)
-    if (passes < kFlowMinPasses) return LIFE_OK;
     CHK(flow_scratch(s, m));
     HIPCHK(hipSetDevice(s.device));
-    // The queue head is a 32-bit counter every resident workgroup bumps once
-    // past the last item: split the passes so that items + grid stays below
-    // 2^31 per launch (life::flow_chunk_passes), flipping the buffer parity
-    // per chunk.
-    const int64_t tiles = life::flow_items_per_pass(L, m);
-    const int64_t per = life::flow_chunk_passes(tiles, life::flow_slots(L), d->flow_chunk);
-    if (per < 1) return LIFE_OK;  // a grid too large for one pass per launch: per-launch tiles
     for (int64_t left = passes; left > 0;) {
         const int64_t n = std::min(left, per);
         Bracket b;
@@ -510,6 +607,48 @@ int step_body(life_dev *d, int64_t generations) {
     return LIFE_OK;
 }
 
+// The row regions per pass this step call pipelines its per-launch tile
+// passes in (pipelined_pass), 0 when it does not: LIFE_OPT_PIPELINE off; not
+// a single shard wrapping both axes in the stencil; a small-grid or
+// one-generation call; timing that gives every launch its own event pair or
+// dispatch stamps (overlapping kernels have no time of their own; the call's
+// one pair, span-only timing and no timing pipeline); fewer than 2 passes
+// behind the dataflow form's share; no plan for the first pass's tile grid.
+int pipe_regions(const life_dev *d, int64_t generations) {
+    if (d->pipe == 0 || d->shards.size() != 1 || d->world != 1 || part(d, 0) || part(d, 1) || self_wrap_x(d) ||
+        !temporal(d) || small_grid(d))
+        return 0;
+    if (d->timing && d->launch_events && timing_mode() != kTimeCall && timing_mode() != kTimeOff) return 0;
+    int form = 0, fm = 0;
+    int64_t per = 0;
+    const int64_t rest = generations - flow_passes(d, generations, &form, &fm, &per) * fm;
+    const int bmax = max_pass_gens(d);
+    const int64_t passes = (rest + bmax - 1) / bmax;
+    if (passes < 2) return 0;
+    const life_layout &L = d->shards[0].lay;
+    const life::TileGeom g = life::tile_geom(L, (int)((rest + passes - 1) / passes));
+    int R = d->pipe;
+    if (R == 1) {
+        R = kPipeAutoRegions;
+        const int slots = life::tile_slots(L);
+        if (passes < kPipeAutoPasses || slots < 1 ||
+            (double)life::region_items(g, life::TileRegion{0, g.ntx, 0, g.nty}) < kPipeAutoRounds * R * slots)
+            return 0;
+    }
+    return life::pipe_plan(g.nty, tile_bands(g), R, 2).R;
+}
+
+// step_body, then the second compute stream of a pipelined call joined back
+// into the first: what follows the call there (its closing event, the
+// census, a gather, fill_random, the next call) stays ordered behind it.
+int call_body(life_dev *d, int64_t generations) {
+    const int rc = step_body(d, generations);
+    const bool piped = d->pipe_call.R > 0;
+    d->pipe_call.R = 0;
+    if (rc == LIFE_OK && piped) CHK(join_stream2(d->shards[0]));
+    return rc;
+}
+
 int step_call(life_dev *d, int64_t generations) {
     // Entry fence: the second compute stream and the comm stream start after
     // everything already queued on the compute stream (an asynchronous
@@ -517,7 +656,17 @@ int step_call(life_dev *d, int64_t generations) {
     // which the overlapped schedule would otherwise race.  A single shard
     // with no partitioned or self-wrapped axis steps on the compute stream
     // alone: no fence (4 runtime calls off a ~1 ms call's critical path).
+    // A pipelined call of such a shard uses the second compute stream too:
+    // it is fenced here and joined back at the end (call_body), and is as good
+    // as one stream to what brackets the call.
     const bool one_stream = d->shards.size() == 1 && !part(d, 0) && !part(d, 1) && !self_wrap_x(d);
+    d->pipe_call.R = 0;
+    if (one_stream) {
+        HIPCHK(hipSetDevice(d->shards[0].device));
+        d->pipe_call.R = pipe_regions(d, generations);
+        d->pipe_call.m = 0;
+        if (d->pipe_call.R > 0) CHK(fence_stream2(d->shards[0]));
+    }
     for (Shard &s : d->shards) {
         if (one_stream) break;
         HIPCHK(hipSetDevice(s.device));
@@ -533,7 +682,7 @@ int step_call(life_dev *d, int64_t generations) {
         if (!d->call_timer) return rc;
         d->call_timer->launches = 0;
         HIPCHK(hipEventRecord(d->call_timer->a, s.stream));
-        rc = step_body(d, generations);
+        rc = call_body(d, generations);
         TimedLaunch *t = d->call_timer;
         d->call_timer = nullptr;
         if (rc != LIFE_OK) {
@@ -548,7 +697,7 @@ int step_call(life_dev *d, int64_t generations) {
         d->call_spans = true;
         return LIFE_OK;
     }
-    if (!d->timing) return step_body(d, generations);
+    if (!d->timing) return call_body(d, generations);
     // timing on, any other call: one event at each end of the call on every
     // shard's compute stream (the entry fence above orders the other streams
     // after the first; every schedule joins them back into it at the end)
@@ -558,7 +707,7 @@ int step_call(life_dev *d, int64_t generations) {
         if (!s.own_b) HIPCHK(hipEventCreate(&s.own_b));
         HIPCHK(hipEventRecord(s.own_a, s.stream));
     }
-    CHK(step_body(d, generations));
+    CHK(call_body(d, generations));
     for (Shard &s : d->shards) {
         HIPCHK(hipSetDevice(s.device));
         HIPCHK(hipEventRecord(s.own_b, s.stream));
