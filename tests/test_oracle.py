@@ -137,3 +137,86 @@ def test_fill_random_window_matches_full_grid(oracle):
     w = oracle.fill_random_window(nx, -50, 3, 120, 20, 7, 0.5)
     np.testing.assert_array_equal(w, np.roll(g, 50, axis=1)[3:23, :120])
     np.testing.assert_array_equal(oracle.fill_random_window(nx, 0, 0, nx, ny, 7, 0.5), g)
+
+
+# The generator and the census mix in plain Python integers (arbitrary
+# precision, masked to 64 bits): no C, no numpy, nothing shared with
+# life_oracle.c, oracle.checksum or the device code.
+_M64 = (1 << 64) - 1
+
+
+def _py_splitmix64(z):
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _py_cell(seed, index, density=0.5):
+    return int((_py_splitmix64(_py_splitmix64(seed) ^ index) >> 32) < min(int(density * 2.0**32), 0xFFFFFFFF))
+
+
+def _py_mix(v):
+    t = (v * 0x9E3779B97F4A7C15) & _M64
+    return t ^ (t >> 29)
+
+
+def test_py_splitmix64_is_the_published_generator(oracle):
+    """SplitMix64's first outputs from state 0 (Vigna's splitmix64.c test
+    vector), so the restatement above is pinned to something outside this
+    repository; the C one agrees."""
+    assert _py_splitmix64(0) == 0xE220A8397B1DCDAF
+    assert _py_splitmix64(0x9E3779B97F4A7C15) == 0x6E789E6AA1B965F4
+    for z in (0, 1, 2**32 - 1, 2**32, 2**35 + 12345, 2**64 - 1):
+        assert oracle.lib().oracle_splitmix64(z) == _py_splitmix64(z)
+
+
+@pytest.mark.parametrize("shape", ["S1", "S3"])
+def test_window_generator_and_checksum_above_2_32(oracle, lm, shape):
+    """oracle.fill_random_window and oracle.checksum(window, x0, y0, nx) at the
+    places tests/test_gpu_beyond_4g.py reads (indices 2^32 - 1, 2^32 and, for
+    S3, up to 2^35 - 1), cell by cell against the plain-integer restatement:
+    about 200 sampled cells per shape plus the named ones.  S3 itself ends at
+    index 2^35 - 1; a cell above 2^35 is taken from a row past its height, which
+    the window form (it knows only nx) can name."""
+    import test_gpu_beyond_4g as B
+
+    sh = B.SHAPES[shape]
+    nx, ny, seed = sh.nx, sh.ny, B.SOUP_SEED
+    m = B.margin(sh.gens)
+    yline = B.index_line_row(nx, ny)
+    pl = B.places(nx, ny, [(0, 0)], yline, B.first_row_above_4g(B.single_layout(lm, sh), ny), sh.gens)
+    w, h = B.INNER_W + 2 * m, B.INNER_H + 2 * m
+    rng = np.random.default_rng(11)
+    named = {"line": [(nx - 1, yline - 1), (0, yline), (nx - 1, yline), (1, yline)], "corner": [(nx - 1, ny - 1), (0, 0)]}
+    seen = set()
+    for p in pl:
+        x0, y0 = B.inner_origin(p)
+        x0, y0 = x0 - m, y0 - m
+        win = B.oracle_window(oracle, nx, ny, x0, y0, w, h, seed)
+        assert win.shape == (h, w)
+        picks = [((gx - x0) % nx, (gy - y0) % ny) for gx, gy in named.get(p.name, [])]
+        picks += list(zip(rng.integers(0, w, 70).tolist(), rng.integers(0, h, 70).tolist()))
+        for i, j in picks:
+            gx, gy = (x0 + i) % nx, (y0 + j) % ny
+            assert win[j, i] == _py_cell(seed, gy * nx + gx), (p, i, j)
+            seen.add(gy * nx + gx)
+    assert {2**32 - 1, 2**32} <= seen and len(seen) >= 140
+    if shape == "S3":
+        assert 2**35 - 1 in seen
+        hi = oracle.fill_random_window(nx, -3, ny + 5, 8, 2, seed, 0.5)
+        for j in range(2):
+            for i in range(8):
+                idx = (ny + 5 + j) * nx + (i - 3) % nx
+                assert idx > 2**35 and hi[j, i] == _py_cell(seed, idx)
+    # the census of the `line` window at its global place: the part right of
+    # the x seam (x0 = 0) and the part left of it, each hashed in place
+    x0, y0 = B.inner_origin(pl[0])
+    x0, y0 = x0 - m, y0 - m
+    assert pl[0].name == "line" and x0 < 0 < x0 + w and 0 <= y0 < yline
+    rows = min(h, ny - y0)  # S1's window wraps in y: the rows below ny are hashed
+    for gx0, ww in ((0, x0 + w), (nx + x0, -x0)):
+        part = oracle.fill_random_window(nx, gx0, y0, ww, rows, seed, 0.5)
+        ys, xs = np.nonzero(part)
+        want = sum(_py_mix((y0 + int(y)) * nx + gx0 + int(x) + 1) for y, x in zip(ys, xs)) & _M64
+        assert len(ys) > 10000 and oracle.checksum(part, gx0, y0, nx) == want
