@@ -235,11 +235,34 @@ int life_dev_clear(life_dev *d);
  * no-op; n < 0, or xy == NULL with n > 0, is LIFE_EINVAL. */
 int life_dev_set_cells(life_dev *d, const int64_t *xy, int64_t n, int alive);
 
+/* The inverse of life_dev_gather_bits: `packed` is ny rows of ceil(nx/8)
+ * bytes, cell x at bit (x & 7) of byte (x >> 3); bits at and beyond nx in a
+ * row's last byte are ignored.  Replaces the whole state, as life_dev_upload,
+ * at 1/8 of its host buffer, PCIe bytes and device staging: each shard copies
+ * the byte columns covering its block into its kept staging buffer and a
+ * kernel unpacks them into the padded layout (a byte two blocks share goes to
+ * both; each keeps its own cells); the halos are then refilled as after an
+ * upload.  Blocking; valid at any step boundary.  Rank mode: collective, the
+ * same `packed` on every rank, each keeps its block (world > 1 has never
+ * executed).  With life_dev_set_timing on, the unpack launch is one more
+ * timed launch of life_dev_kernel_stats (no bytes booked). */
+int life_dev_upload_bits(life_dev *d, const uint8_t *packed);
+
 /* The periodic window of w x h cells at (x0, y0): cells[j*w + i] (0/1) is
  * cell ((x0 + i) mod nx, (y0 + j) mod ny); x0, y0 any int64, 1 <= w <= nx,
  * 1 <= h <= ny (else LIFE_EINVAL).  Read straight from the padded blocks (up
  * to four wrapped pieces per shard); device staging is w*h bytes. */
 int life_dev_gather_rect(life_dev *d, int64_t x0, int64_t y0, int64_t w, int64_t h, uint8_t *cells);
+
+/* The inverse of life_dev_gather_rect: cell ((x0 + i) mod nx, (y0 + j) mod ny)
+ * becomes cells[j*w + i] != 0; every other cell is untouched.  x0, y0 any
+ * int64; 1 <= w <= nx, 1 <= h <= ny, else LIFE_EINVAL.  The window is staged
+ * (w*h bytes) on every shard it touches and pasted into the padded block in up
+ * to four wrapped pieces; the halos are then refilled as after
+ * life_dev_set_cells (a part-used deep halo included).  Blocking; valid at
+ * any step boundary.  Rank mode: collective with identical arguments on every
+ * rank (world > 1 has never executed). */
+int life_dev_set_rect(life_dev *d, int64_t x0, int64_t y0, int64_t w, int64_t h, const uint8_t *cells);
 
 /* Block-summed density map: ceil(ny/fy) rows of ceil(nx/fx) counts,
  * counts[by*bw + bx] = live cells with x / fx == bx and y / fy == by (the last

@@ -1,7 +1,7 @@
 // life_frames.hip -- moving cells in and out of the device runtime: upload
 // and random fill, life_collect in its three frame formats (dense / VTK /
-// LIFEBITS gather), the census, the sparse I/O (clear, cell lists, window
-// readout, density maps) and the copy benchmark.
+// LIFEBITS gather), the census, the sparse I/O (clear, cell lists, packed-frame
+// upload, window readout and paste, density maps) and the copy benchmark.
 #include "life_dev_internal.h"
 
 using namespace life::rt;
@@ -277,6 +277,39 @@ int life_dev_set_cells(life_dev *d, const int64_t *xy, int64_t n, int alive) {
     return life_dev_sync(d);
 }
 
+int life_dev_upload_bits(life_dev *d, const uint8_t *packed) {
+    if (!d || !packed) return LIFE_EINVAL;
+    CHK(life_dev_sync(d));  // as life_dev_set_cells
+    const int64_t frb = (d->nx + 7) / 8;  // the frame's row bytes (64-bit offsets: 4 GiB at 2^35 cells)
+    for (Shard &s : d->shards) {
+        const life_layout &L = s.lay;
+        HIPCHK(hipSetDevice(s.device));
+        // the byte columns [x0 >> 3, (x0 + w + 7) >> 3) of the shard's rows: a
+        // byte two blocks share (an edge at x % 8 != 0) goes to both, and the
+        // kernel keeps each one's cells
+        const int64_t rb = life::bits_row_bytes(L), sp = life::unbits_pitch(L);
+        uint8_t *stage;
+        CHK(stage_buffer(s, (size_t)(sp * L.h), &stage));
+        // `packed` is the caller's pageable memory: ordered on the shard's
+        // stream and waited for (see life_dev_upload)
+        HIPCHK(hipMemcpy2DAsync(stage, (size_t)sp, packed + L.y0 * frb + (L.x0 >> 3), (size_t)frb, (size_t)rb,
+                                (size_t)L.h, hipMemcpyHostToDevice, s.stream));
+        HIPCHK(hipStreamSynchronize(s.stream));
+        // timing on: the unpack launch takes an event pair of its own and is
+        // counted by life_dev_kernel_stats (no bytes are booked for it)
+        Bracket b;
+        CHK(bracket_begin(d, s, true, 1, kExtNever, true, s.stream, &b));
+        HIPCHK(life::launch_unbits_block(L, stage, s.buf[s.cur], s.stream));
+        CHK(bracket_end(b, s.stream));
+    }
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        HIPCHK(hipStreamSynchronize(s.stream));
+    }
+    CHK(exchange(d, 0, false));  // every apron K deep, the deep-halo count restarts (see life_dev_set_cells)
+    return life_dev_sync(d);
+}
+
 namespace {
 // The pieces of the periodic interval [a, a + len) (a in [0, n), len <= n)
 // inside the block [b0, b0 + bl): at most two, the block seen at b0 and at
@@ -336,6 +369,36 @@ int life_dev_gather_rect(life_dev *d, int64_t x0, int64_t y0, int64_t w, int64_t
         HIPCHK(hipStreamSynchronize(s.stream));
     }
     return LIFE_OK;
+}
+
+int life_dev_set_rect(life_dev *d, int64_t x0, int64_t y0, int64_t w, int64_t h, const uint8_t *cells) {
+    if (!d || !cells || w < 1 || h < 1 || w > d->nx || h > d->ny) return LIFE_EINVAL;
+    CHK(life_dev_sync(d));  // the edit orders behind the work on all three streams
+    const int64_t ax = floor_mod(x0, d->nx), ay = floor_mod(y0, d->ny);
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        const life_layout &L = s.lay;
+        Span sx[2], sy[2];
+        const int kx = wrapped_spans(ax, w, d->nx, L.x0, L.w, sx), ky = wrapped_spans(ay, h, d->ny, L.y0, L.h, sy);
+        if (kx == 0 || ky == 0) continue;  // the window misses this block
+        // the window in device memory, row pitch w; `cells` is the caller's
+        // pageable memory: ordered on the shard's stream and waited for below
+        uint8_t *win;
+        CHK(stage_buffer(s, (size_t)(w * h), &win));
+        HIPCHK(hipMemcpyAsync(win, cells, (size_t)(w * h), hipMemcpyHostToDevice, s.stream));
+        // in order on the one stream: with w == nx and x0 % 64 != 0 the two
+        // pieces of a row share a 64-cell pair
+        for (int j = 0; j < ky; j++)
+            for (int i = 0; i < kx; i++)
+                HIPCHK(life::launch_paste_piece(L, s.buf[s.cur], sx[i].blk, sy[j].blk, sx[i].len, sy[j].len,
+                                                win + sy[j].win * w + sx[i].win, w, s.stream));
+    }
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        HIPCHK(hipStreamSynchronize(s.stream));
+    }
+    CHK(exchange(d, 0, false));  // as life_dev_set_cells: every apron refilled, a part-used deep halo restarted
+    return life_dev_sync(d);
 }
 
 int life_dev_gather_density(life_dev *d, int64_t fx, int64_t fy, uint32_t *counts) {

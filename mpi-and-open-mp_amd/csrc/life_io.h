@@ -57,6 +57,12 @@ hipError_t launch_vtk_block(const life_layout &L, const uint8_t *buf, uint8_t *o
 // bit x0 & 7 of its first byte on.
 inline int64_t bits_row_bytes(const life_layout &L) { return ((L.x0 & 7) + L.w + 7) / 8; }
 hipError_t launch_bits_block(const life_layout &L, const uint8_t *buf, uint8_t *out, hipStream_t s);
+// The way back: `in` holds the same bits_row_bytes(L) bytes per owned row at
+// row pitch unbits_pitch(L) (16-B aligned loads; the bytes between the two
+// need not be set).  Writes every 16-B unit of the owned rows, cells at and
+// beyond w as 0; the aprons are the caller's to refill.
+inline int64_t unbits_pitch(const life_layout &L) { return (bits_row_bytes(L) + 15) / 16 * 16; }
+hipError_t launch_unbits_block(const life_layout &L, const uint8_t *in, uint8_t *buf, hipStream_t s);
 
 // Counter-based synthetic init of the owned cells (global indices).
 hipError_t launch_fill_random(const life_layout &L, int64_t nx, uint64_t key, uint32_t thr32,
@@ -76,6 +82,11 @@ hipError_t launch_set_cells(const life_layout &L, int64_t nx, int64_t ny, const 
 // out[j * opitch + i].
 hipError_t launch_rect_piece(const life_layout &L, const uint8_t *buf, int64_t lx0, int64_t ly0, int64_t pw,
                              int64_t ph, uint8_t *out, int64_t opitch, hipStream_t s);
+// The way back: block cells [lx0, lx0 + pw) x [ly0, ly0 + ph) (owned) become
+// in[j * ipitch + i] != 0; nothing else is written.  Pieces that share a
+// 64-cell pair of a row must be launched in order on one stream.
+hipError_t launch_paste_piece(const life_layout &L, uint8_t *buf, int64_t lx0, int64_t ly0, int64_t pw, int64_t ph,
+                              const uint8_t *in, int64_t ipitch, hipStream_t s);
 // Adds the block's live cells to the density map: map[(y / fy) * bw + x / fx]
 // over global (x, y); bw = bins per map row.
 hipError_t launch_density(const life_layout &L, const uint8_t *buf, int64_t fx, int64_t fy, int64_t bw,

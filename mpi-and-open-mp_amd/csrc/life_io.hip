@@ -303,6 +303,49 @@ __global__ void bits_kernel(const uint8_t *buf, const BlockView blk, int s, uint
     }
 }
 
+// The inverse (life_dev_upload_bits): `in` holds, per owned row and at row
+// pitch `ipitch` (a multiple of 16), the rb = bits_row_bytes packed bytes that
+// cover the block, so block cell c sits at bit s + c of its row, s = x0 & 7.
+// One thread per 16-byte unit of an owned row; 2-D grid, y strides rows.  Bit
+// encoding: the unit's 128 cells are bits [s + 128u, s + 128u + 128) -- one
+// aligned 16-B load plus the byte the shift pulls in (read only when it is
+// one of the rb, i.e. when it can hold a cell below w), a funnel shift, then
+// pair_of per 64 cells.  Byte encoding: 16 cells from 2-3 bytes, a nibble per
+// dword.  Whole units are stored as in import_kernel: the cells at and beyond
+// w become 0 and the caller's exchange fills the aprons.
+__device__ __forceinline__ uint64_t low_mask64(int64_t n) {  // the n lowest bits, n clamped to 0..64
+    return n <= 0 ? 0ull : n >= 64 ? ~0ull : (~0ull >> (64 - n));
+}
+template <bool BIT>
+__global__ void unbits_kernel(const uint8_t *in, int64_t ipitch, int64_t rb, int s, uint8_t *buf,
+                              const BlockView blk) {
+    const auto [pitch, ya, xoff, w, h, units, gx0, gy0] = blk;
+    const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= units) return;
+    const int64_t valid = w - u * (BIT ? 128 : 16);  // cells of this unit inside the block (>= 1)
+    const int64_t xb = BIT ? 16 * u + 16 : 2 * u + 2;  // the byte after the unit's aligned ones
+    const bool extra = s != 0 && xb < rb;
+    for (int64_t y = blockIdx.y; y < h; y += gridDim.y) {
+        const uint8_t *row = in + y * ipitch;
+        const uint32_t e = extra ? row[xb] : 0u;
+        uint4 q;
+        if (BIT) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(row + 16 * u);
+            uint64_t lo = (uint64_t)v.x | ((uint64_t)v.y << 32), hi = (uint64_t)v.z | ((uint64_t)v.w << 32);
+            if (s) {
+                lo = (lo >> s) | (hi << (64 - s));
+                hi = (hi >> s) | ((uint64_t)e << (64 - s));
+            }
+            const uint2 p0 = pair_of(lo & low_mask64(valid)), p1 = pair_of(hi & low_mask64(valid - 64));
+            q = make_uint4(p0.x, p0.y, p1.x, p1.y);
+        } else {
+            const uint32_t v = *reinterpret_cast<const uint16_t *>(row + 2 * u) | (e << 16);
+            q = unpack_half((v >> s) & (uint32_t)low_mask64(valid < 16 ? valid : 16), 0);
+        }
+        *reinterpret_cast<uint4 *>(buf + (y + ya) * pitch + xoff + 16 * u) = q;
+    }
+}
+
 __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -448,6 +491,40 @@ __global__ void rect_kernel(const uint8_t *buf, const BlockView blk, int64_t lx0
         }
         uint8_t *o = out + j * opitch + i0;
         for (int k = 0; k < n; ++k) o[k] = (uint8_t)((c >> k) & 1u);
+    }
+}
+
+// The inverse (life_dev_set_rect): block cells [lx0, lx0 + pw) x [ly0, ly0 +
+// ph) become in[j * ipitch + i] != 0; the aprons and every cell outside the
+// piece stay as they are.  2-D grid, y strides rows.  Bit encoding: one thread
+// per 64-cell pair the piece touches -- its bytes of that pair gathered into
+// natural order, then a read-modify-write of the pair under the mask of the
+// covered cells: one thread of a launch owns a dword, so no atomics; two
+// pieces of one row that share a pair (w == nx, x0 % 64 != 0) are two launches
+// in order on one stream.  Byte encoding: one thread per cell, a plain store.
+template <bool BIT>
+__global__ void paste_kernel(uint8_t *buf, const BlockView blk, int64_t lx0, int64_t ly0, int64_t pw, int64_t ph,
+                             const uint8_t *in, int64_t ipitch) {
+    const auto [pitch, ya, xoff, w, h, units, gx0, gy0] = blk;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!BIT) {
+        if (t >= pw) return;
+        for (int64_t j = blockIdx.y; j < ph; j += gridDim.y)
+            buf[(ly0 + j + ya) * pitch + xoff + lx0 + t] = in[j * ipitch + t] != 0;
+        return;
+    }
+    const int64_t p = (lx0 >> 6) + t;  // this thread's pair: cells [64p, 64p + 64)
+    const int64_t a = p * 64 > lx0 ? p * 64 : lx0, b = p * 64 + 64 < lx0 + pw ? p * 64 + 64 : lx0 + pw;
+    if (a >= b) return;  // past the piece's last pair
+    const uint32_t sh = (uint32_t)(a - p * 64);
+    const int n = (int)(b - a);
+    const uint64_t mask = low_mask64(n) << sh;
+    for (int64_t j = blockIdx.y; j < ph; j += gridDim.y) {
+        const uint8_t *src = in + j * ipitch + (a - lx0);
+        uint64_t v = 0;
+        for (int k = 0; k < n; ++k) v |= (uint64_t)(src[k] != 0) << k;
+        uint32_t *wd = reinterpret_cast<uint32_t *>(buf + (ly0 + j + ya) * pitch + xoff);
+        put_pair(wd, p, (pair_nat(wd, p) & ~mask) | (v << sh));
     }
 }
 
@@ -600,6 +677,13 @@ hipError_t launch_bits_block(const life_layout &L, const uint8_t *buf, uint8_t *
     return launch_enc(L, bits_kernel<true>, bits_kernel<false>, grid, s, buf, view(L), sh, out, rb);
 }
 
+hipError_t launch_unbits_block(const life_layout &L, const uint8_t *in, uint8_t *buf, hipStream_t s) {
+    const int sh = (int)(L.x0 & 7);
+    const dim3 grid(blocks_for(L.units, 256), (unsigned)(L.h < 8192 ? L.h : 8192));
+    return launch_enc(L, unbits_kernel<true>, unbits_kernel<false>, grid, s, in, unbits_pitch(L), bits_row_bytes(L), sh,
+                      buf, view(L));
+}
+
 hipError_t launch_copy(const void *in, void *out, int64_t bytes, hipStream_t s) {
     const int64_t n = bytes / 16;
     copy_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(reinterpret_cast<const uint4 *>(in),
@@ -625,6 +709,14 @@ hipError_t launch_rect_piece(const life_layout &L, const uint8_t *buf, int64_t l
     if (lx0 < 0 || ly0 < 0 || pw < 1 || ph < 1 || lx0 + pw > L.w || ly0 + ph > L.h) return hipErrorInvalidValue;
     const dim3 grid(blocks_for((pw + 7) / 8, 256), (unsigned)(ph < 8192 ? ph : 8192));
     return launch_enc(L, rect_kernel<true>, rect_kernel<false>, grid, s, buf, view(L), lx0, ly0, pw, ph, out, opitch);
+}
+
+hipError_t launch_paste_piece(const life_layout &L, uint8_t *buf, int64_t lx0, int64_t ly0, int64_t pw, int64_t ph,
+                              const uint8_t *in, int64_t ipitch, hipStream_t s) {
+    if (lx0 < 0 || ly0 < 0 || pw < 1 || ph < 1 || lx0 + pw > L.w || ly0 + ph > L.h) return hipErrorInvalidValue;
+    const int64_t lanes = is_bit(L) ? ((lx0 + pw - 1) >> 6) - (lx0 >> 6) + 1 : pw;  // pairs touched / cells
+    const dim3 grid(blocks_for(lanes, 256), (unsigned)(ph < 8192 ? ph : 8192));
+    return launch_enc(L, paste_kernel<true>, paste_kernel<false>, grid, s, buf, view(L), lx0, ly0, pw, ph, in, ipitch);
 }
 
 hipError_t launch_density(const life_layout &L, const uint8_t *buf, int64_t fx, int64_t fy, int64_t bw,

@@ -31,7 +31,13 @@
  *                     grid is never allocated; same cells, same frames.  With
  *                     --format density a pattern in a 65536^2 universe needs
  *                     kilobytes on the host
- *   --resume FILE     start from a .bits dump instead of the .cfg cells
+ *   --resume FILE     start from a .bits dump instead of the .cfg cells: the
+ *                     dump sets nx and ny and goes to the device packed
+ *                     (life_dev_upload_bits); frames continue its numbering
+ *   --at X,Y          with --resume: the dump is a pattern, pasted with its
+ *                     first cell at (X, Y) (any integers, wrapped) into an
+ *                     empty universe of --nx x --ny cells (both required;
+ *                     life_dev_clear + life_dev_set_rect); the dump must fit
  *   --live            print the live-cell count after the run to stderr
  *   --rank-mode       one-process-per-GPU mode even without a launcher (world 1)
  *
@@ -297,7 +303,9 @@ static int save_density(const char *path, int64_t nx, int64_t ny, int64_t fx, in
     return fclose(f) == 0 && ok ? LIFE_OK : LIFE_EIO;
 }
 
-static int load_bits(const char *path, int64_t *nx, int64_t *ny, int64_t *gen, uint8_t **grid) {
+/* A save_bits frame, still packed: ny rows of ceil(nx/8) bytes read as one
+ * block (what life_dev_upload_bits takes; no nx*ny grid). */
+static int load_bits(const char *path, int64_t *nx, int64_t *ny, int64_t *gen, uint8_t **packed) {
     FILE *f = fopen(path, "r");
     if (!f) return LIFE_EIO;
     long long v, a, b, g;
@@ -306,15 +314,9 @@ static int load_bits(const char *path, int64_t *nx, int64_t *ny, int64_t *gen, u
         fclose(f);
         return LIFE_EIO;
     }
-    const int64_t rb = (a + 7) / 8;
-    uint8_t *row = (uint8_t *)malloc((size_t)rb);
-    uint8_t *out = (uint8_t *)malloc((size_t)(a * b));
-    int ok = row && out;
-    for (int64_t y = 0; y < b && ok; y++) {
-        ok = fread(row, 1, (size_t)rb, f) == (size_t)rb;
-        for (int64_t x = 0; x < a && ok; x++) out[y * a + x] = (uint8_t)((row[x >> 3] >> (x & 7)) & 1u);
-    }
-    free(row);
+    const size_t n = (size_t)(b * ((a + 7) / 8));
+    uint8_t *out = (uint8_t *)malloc(n);
+    const int ok = out && fread(out, 1, n, f) == n;
     fclose(f);
     if (!ok) {
         free(out);
@@ -323,14 +325,26 @@ static int load_bits(const char *path, int64_t *nx, int64_t *ny, int64_t *gen, u
     *nx = a;
     *ny = b;
     *gen = g;
-    *grid = out;
+    *packed = out;
     return LIFE_OK;
+}
+
+/* --at: the dump as a dense window of its own size, cells[j*w + i] 0/1 (what
+ * life_dev_set_rect takes). */
+static uint8_t *unpack_bits(const uint8_t *packed, int64_t w, int64_t h) {
+    const int64_t rb = (w + 7) / 8;
+    uint8_t *out = (uint8_t *)malloc((size_t)(w * h));
+    if (!out) return NULL;
+    for (int64_t y = 0; y < h; y++)
+        for (int64_t x = 0; x < w; x++) out[y * w + x] = (uint8_t)((packed[y * rb + (x >> 3)] >> (x & 7)) & 1u);
+    return out;
 }
 
 int main(int argc, char **argv) {
     const char *cfg_path = NULL, *resume = NULL;
     int gpus = 1, kernel = LIFE_KERNEL_BIT, vtk = 1, live = 0, have_random = 0, bits = 0, force_rank = 0;
-    int partition = LIFE_PARTITION_CART, sparse = 0;
+    int partition = LIFE_PARTITION_CART, sparse = 0, have_at = 0;
+    long long at_x = 0, at_y = 0; /* --at X,Y */
     long long dfx = 0, dfy = 0; /* --format density:FX[xFY] (bits == 2) */
     long long o_nx = -1, o_ny = -1, o_steps = -1, o_save = -1;
     unsigned long long seed = 0;
@@ -378,6 +392,20 @@ int main(int argc, char **argv) {
             }
         } else if (!strcmp(s, "--sparse")) sparse = 1;
         else if (!strcmp(s, "--resume") && more) resume = argv[++a];
+        else if (!strcmp(s, "--at") && more) {
+            char *end;
+            at_x = strtoll(argv[++a], &end, 10);
+            have_at = end != argv[a] && *end == ',';
+            if (have_at) {
+                const char *ys = end + 1;
+                at_y = strtoll(ys, &end, 10);
+                have_at = end != ys && !*end;
+            }
+            if (!have_at) {
+                fprintf(stderr, "life_mi355x: --at takes X,Y (two integers)\n");
+                return 1;
+            }
+        }
         else if (!strcmp(s, "--live")) live = 1;
         else if (!strcmp(s, "--rank-mode")) force_rank = 1;
         else if (s[0] != '-' && !cfg_path) cfg_path = s;
@@ -387,9 +415,17 @@ int main(int argc, char **argv) {
             break;
         }
     }
+    if (have_at && !resume) {
+        fprintf(stderr, "life_mi355x: --at places a --resume dump: it needs --resume FILE\n");
+        return 1;
+    }
     if (!cfg_path && !have_random && !resume) {
         printf("Usage: %s input file.\n", argv[0]); /* life_cart.c:53-56 */
         return 0;
+    }
+    if (have_at && (o_nx <= 0 || o_ny <= 0)) {
+        fprintf(stderr, "life_mi355x: --at needs the universe's size: --nx N --ny N\n");
+        return 1;
     }
     if (kernel < 0 || gpus < 1 || bits < 0 || partition < 0) {
         fprintf(stderr, "life_mi355x: bad --kernel/--gpus/--format/--partition\n");
@@ -416,14 +452,24 @@ int main(int argc, char **argv) {
         fprintf(stderr, "life_mi355x: cannot read config '%s'\n", cfg_path);
         return 1;
     }
-    uint8_t *resumed = NULL;
+    uint8_t *resumed = NULL; /* the dump's packed rows */
     int64_t gen0 = 0; /* generation the run starts from (a --resume dump's) */
-    if (resume && load_bits(resume, &c.nx, &c.ny, &gen0, &resumed) != LIFE_OK) {
+    int64_t dump_nx = 0, dump_ny = 0;
+    if (resume && load_bits(resume, &dump_nx, &dump_ny, &gen0, &resumed) != LIFE_OK) {
         fprintf(stderr, "life_mi355x: cannot read dump '%s'\n", resume);
         return 1;
     }
-    if (o_nx > 0 && !resume) c.nx = o_nx;
-    if (o_ny > 0 && !resume) c.ny = o_ny;
+    if (resume && !have_at) { /* the dump is the universe */
+        c.nx = dump_nx;
+        c.ny = dump_ny;
+    }
+    if (o_nx > 0 && (!resume || have_at)) c.nx = o_nx;
+    if (o_ny > 0 && (!resume || have_at)) c.ny = o_ny;
+    if (have_at && (dump_nx > c.nx || dump_ny > c.ny)) {
+        fprintf(stderr, "life_mi355x: the dump '%s' (%lld x %lld) does not fit the %lld x %lld universe\n", resume,
+                (long long)dump_nx, (long long)dump_ny, (long long)c.nx, (long long)c.ny);
+        return 1;
+    }
     if (o_steps >= 0) c.steps = o_steps;
     if (o_save >= 0) c.save_steps = o_save;
     if (c.nx <= 0 || c.ny <= 0 || c.steps < 0 || c.save_steps <= 0) {
@@ -480,8 +526,14 @@ int main(int argc, char **argv) {
         body = (char *)malloc((size_t)(2 * c.nx * c.ny));
         if (!body) die("host frame", LIFE_ENOMEM);
     }
-    if (resume) {
-        rc = life_dev_upload(d, resumed);
+    if (resume && have_at) {
+        uint8_t *win = unpack_bits(resumed, dump_nx, dump_ny);
+        if (!win) die("host window", LIFE_ENOMEM);
+        if ((rc = life_dev_clear(d)) == LIFE_OK) rc = life_dev_set_rect(d, at_x, at_y, dump_nx, dump_ny, win);
+        free(win);
+        free(resumed);
+    } else if (resume) {
+        rc = life_dev_upload_bits(d, resumed);
         free(resumed);
     } else if (have_random) {
         rc = life_dev_fill_random(d, seed, density >= 1.0 ? 0xFFFFFFFFu : (uint32_t)(density * 4294967296.0));

@@ -29,8 +29,8 @@ import sys
 
 import numpy as np
 
-from .cfg import (bits_bytes, density_bytes, load_bits, load_cfg, load_cfg_cells, load_density,  # noqa: F401
-                  save_vtk, vtk_bytes, vtk_header)
+from .cfg import (bits_bytes, density_bytes, load_bits, load_bits_packed, load_cfg, load_cfg_cells,  # noqa: F401
+                  load_density, save_vtk, vtk_bytes, vtk_header)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # LIFE_MI355X_LIB: load another build of the same library (experiments only)
@@ -65,6 +65,7 @@ ABI_SYMBOLS = (
     "life_dev_barrier", "life_device_count", "life_dev_last_path", "life_dev_call_stats",
     "life_dev_strerror", "life_dev_shard_info",
     "life_dev_clear", "life_dev_set_cells", "life_dev_gather_rect", "life_dev_gather_density",
+    "life_dev_upload_bits", "life_dev_set_rect",
 )
 PATHS = {0: "none", 1: "onegen", 2: "tiles", 3: "flow", 5: "small"}
 
@@ -149,6 +150,8 @@ def _lib():
         L.life_dev_set_cells.argtypes = [vp, P(i64), i64, i32]
         L.life_dev_gather_rect.argtypes = [vp, i64, i64, i64, i64, P(ctypes.c_uint8)]
         L.life_dev_gather_density.argtypes = [vp, i64, i64, P(ctypes.c_uint32)]
+        L.life_dev_upload_bits.argtypes = [vp, P(ctypes.c_uint8)]
+        L.life_dev_set_rect.argtypes = [vp, i64, i64, i64, i64, P(ctypes.c_uint8)]
         L.life_dev_live_count.argtypes = [vp]
         L.life_dev_live_count.restype = i64
         L.life_dev_sync.argtypes = [vp]
@@ -344,6 +347,30 @@ class Life:
             raise ValueError(f"set_cells: cells must have shape (n, 2), not {c.shape}")
         _check(_lib().life_dev_set_cells(self._h, c.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), c.shape[0],
                                          1 if alive else 0), "set_cells")
+
+    def upload_bits(self, packed: np.ndarray) -> None:
+        """life_dev_upload_bits, the inverse of :meth:`gather_bits`: the whole
+        state from packed rows, a uint8 (ny, ceil(nx/8)) array with cell x at
+        bit x & 7 of byte x >> 3 (np.packbits(grid, axis=1,
+        bitorder="little")); a row's bits at and beyond nx are ignored."""
+        p = np.asarray(packed)
+        if p.dtype != np.uint8 or p.shape != (self.ny, (self.nx + 7) // 8):
+            raise ValueError(f"upload_bits: packed must be uint8 of shape ({self.ny}, {(self.nx + 7) // 8}), "
+                             f"not {p.dtype} {p.shape}")
+        p = np.ascontiguousarray(p)
+        _check(_lib().life_dev_upload_bits(self._h, p.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))), "upload_bits")
+
+    def set_rect(self, x0: int, y0: int, cells) -> None:
+        """life_dev_set_rect, the inverse of :meth:`gather_rect`: cell
+        ((x0 + i) mod nx, (y0 + j) mod ny) becomes cells[j, i] != 0 for the
+        (h, w) integer or bool array `cells`; other cells are untouched."""
+        c = np.asarray(cells)
+        if c.ndim != 2 or not (np.issubdtype(c.dtype, np.integer) or c.dtype == np.bool_):
+            raise ValueError(f"set_rect: cells must be a 2-D integer or bool array, not {c.dtype} {c.shape}")
+        # uint8 goes as it is (the library takes any nonzero byte as alive); wider values must not be cut to 8 bits
+        c = np.ascontiguousarray(c if c.dtype == np.uint8 else c != 0, dtype=np.uint8)
+        _check(_lib().life_dev_set_rect(self._h, int(x0), int(y0), c.shape[1], c.shape[0],
+                                        c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))), "set_rect")
 
     def gather_rect(self, x0: int, y0: int, w: int, h: int, out: np.ndarray | None = None) -> np.ndarray:
         """The periodic w x h window at (x0, y0) as an (h, w) uint8 array:

@@ -9,7 +9,9 @@
   ASCII STRUCTURED_POINTS, one ``%d\\n`` per cell, y outer, x inner.
 * ``load_cfg_cells`` is the same parser without the grid: the coordinate list
   for ``Life.set_cells``; ``density_bytes`` / ``load_density`` are the
-  driver's density-map frames.
+  driver's density-map frames; ``bits_bytes`` / ``load_bits`` /
+  ``load_bits_packed`` its packed LIFEBITS frames (the last one without
+  unpacking, for ``Life.upload_bits``).
 """
 from __future__ import annotations
 
@@ -79,8 +81,9 @@ def bits_bytes(grid: np.ndarray, generation: int = 0) -> bytes:
     return f"LIFEBITS 1 {nx} {ny} {generation}\n".encode() + rows.tobytes()
 
 
-def load_bits(path: str):
-    """-> (generation, grid[ny, nx] uint8) of a --format bits frame."""
+def load_bits_packed(path: str):
+    """-> (generation, nx, ny, packed[ny, ceil(nx/8)] uint8) of a --format bits
+    frame, still packed: what Life.upload_bits takes (no nx*ny grid)."""
     with open(path, "rb") as f:
         head = f.readline().split()
         if len(head) != 5 or head[0] != b"LIFEBITS" or head[1] != b"1":
@@ -90,7 +93,13 @@ def load_bits(path: str):
     rb = (nx + 7) // 8
     if raw.size != rb * ny:
         raise ValueError(f"{path}: truncated")
-    grid = np.unpackbits(raw.reshape(ny, rb), axis=1, bitorder="little")[:, :nx]
+    return gen, nx, ny, raw.reshape(ny, rb)
+
+
+def load_bits(path: str):
+    """-> (generation, grid[ny, nx] uint8) of a --format bits frame."""
+    gen, nx, _, packed = load_bits_packed(path)
+    grid = np.unpackbits(packed, axis=1, bitorder="little")[:, :nx]
     return gen, np.ascontiguousarray(grid, dtype=np.uint8)
 
 
