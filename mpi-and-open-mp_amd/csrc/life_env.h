@@ -52,6 +52,8 @@ constexpr IntKnob kTemporalRowsByte{"LIFE_TEMPORAL_ROWS_BYTE", 48, 32, 48};
 constexpr FlagKnob kByteOneGhost{"LIFE_BYTE_ONE_GHOST", 1};
 // banded last tile column of the bit tiles; 0: full-width tiles (A/B knob, read by tests)
 constexpr FlagKnob kBands{"LIFE_BANDS", 1};
+// that column as up to two sub-columns (life::band_split); 0: one band, only when it owns <= 30 pairs (A/B knob)
+constexpr FlagKnob kBandSplit{"LIFE_BAND_SPLIT", 1};
 // the same for the dataflow form (A/B knob, read by tests)
 constexpr FlagKnob kFlowBands{"LIFE_FLOW_BANDS", 1};
 // bit tiles in per-XCD row-major runs; 0: dispatch order (profiles/r03/r5a)

@@ -83,6 +83,38 @@ struct PipePlan {
     bool record[kPipeMaxRegions] = {};
 };
 PipePlan pipe_plan(int64_t nty, int64_t B, int R, int S);
+
+// The banded last tile column of the bit tiles.  A tile column that owns o
+// < 62 pairs runs as up to kMaxBands contiguous sub-columns, each in groups
+// of G = 2^gsh lanes (1 ghost + own owned + ghost pairs, own <= G - 2, 2 <=
+// gsh <= 5), 64 / G tile rows per workgroup.  band_split(o) minimises the
+// lanes a tile row of the column takes, the sum of G over its sub-columns: one
+// sub-column at the smallest G that holds o when no pair of sub-columns takes
+// fewer lanes (ties keep one), else the pair with the widest first part
+// (o = 32: {30, G 32} + {2, G 4}, 36 lanes); n == 0, a whole 64-lane tile,
+// when nothing takes fewer than 64 (o >= 45).
+constexpr int kMaxBands = 2;
+struct BandCol { int first, own, gsh; };  // first pair within the column, owned pairs, log2 of the group
+struct BandSplit {
+    int n = 0;
+    BandCol b[kMaxBands] = {};
+};
+BandSplit band_split(int64_t o, int max_parts = kMaxBands);  // max_parts 1: one sub-column (o <= 30) or none
+// Tile rows per banded item of each sub-column (64 >> gsh, powers of two).
+struct BandRows {
+    int n = 0;
+    int64_t B[kMaxBands] = {};
+    int64_t largest() const {  // a multiple of every other
+        int64_t m = 1;
+        for (int i = 0; i < n; i++) m = B[i] > m ? B[i] : m;
+        return m;
+    }
+};
+// pipe_plan with the regions aligned on the largest band (whole banded items
+// of every sub-column)
+inline PipePlan pipe_plan(int64_t nty, const BandRows &bands, int R, int S) {
+    return pipe_plan(nty, bands.largest(), R, S);
+}
 #pragma GCC visibility pop
 
 // The dataflow queue head is 32-bit: one launch may hold at most
@@ -147,5 +179,19 @@ inline int64_t tail_row_items(int64_t ntx, int64_t B, int64_t rows) {
 double tail_makespan2(int64_t ntx, int64_t B, int64_t F_rows, int64_t n2, int64_t slots, double c, int64_t pre = 0);
 TailPlan tail_plan(int64_t ntx, int64_t B, int64_t ty0, int64_t ty1, int64_t yend, int64_t T, int64_t T2,
                    int64_t slots, int mode, double c, int64_t pre = 0);
+// The same with the band list: nfull ordinary tile columns, then the last
+// column's sub-columns; r tile rows take nfull r + sum ceil(r / B_i) items.
+// The forms above are the one-band case (nfull = ntx - 1, {B}; B <= 1: ntx
+// ordinary columns, no bands).
+inline int64_t tail_row_items(int64_t nfull, const BandRows &bands, int64_t rows) {
+    if (rows <= 0) return 0;
+    int64_t n = nfull * rows;
+    for (int i = 0; i < bands.n; i++) n += (rows + bands.B[i] - 1) / bands.B[i];
+    return n;
+}
+double tail_makespan2(int64_t nfull, const BandRows &bands, int64_t F_rows, int64_t n2, int64_t slots, double c,
+                      int64_t pre = 0);
+TailPlan tail_plan(int64_t nfull, const BandRows &bands, int64_t ty0, int64_t ty1, int64_t yend, int64_t T,
+                   int64_t T2, int64_t slots, int mode, double c, int64_t pre = 0);
 
 }  // namespace life

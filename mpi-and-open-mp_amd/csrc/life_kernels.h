@@ -62,13 +62,22 @@ struct TileGeom {
     int64_t lanes;  // owned lane columns per tile (62)
     int64_t cells;  // cells per lane column: 64 (bit pairs) or 32 (byte words)
     int64_t rows, ntx, nty;
-    int gsh;       // < 6: tile column bcol runs as bands of 2^gsh lanes (64 >> gsh tile rows per workgroup)
+    // nband > 0: tile column bcol runs as nband sub-columns of banded items
+    // (life::band_split of the pairs it owns: groups of 2^gsh lanes, 64 >>
+    // gsh tile rows per workgroup)
+    int nband;
+    BandCol band[kMaxBands];
     int64_t bcol;  // the banded column (ntx - 1), -1 without banding
 };
-TileGeom tile_geom(const life_layout &L, int m);
-// workgroups (items) one launch of region r takes: its full tiles, plus its
-// banded items when it holds the banded column
+// one_band: at most one sub-column, and only a column owning <= 30 pairs (the
+// dataflow form's geometry; LIFE_BAND_SPLIT=0 gives it everywhere)
+TileGeom tile_geom(const life_layout &L, int m, bool one_band = false);
+// workgroups (items) one launch of region r takes: its full tiles, plus the
+// banded items of every sub-column when it holds the banded column
 int64_t region_items(const TileGeom &g, const TileRegion &r);
+// tile rows per banded item of each sub-column of the tile columns [.., tx1)
+// (none unless the region holds the banded column)
+BandRows region_bands(const TileGeom &g, int64_t tx1);
 int tile_ghost(const life_layout &L, int m);  // ghost rows per window end: m (bit), K or 1 (byte, m = 1)
 // Rows a temporally blocked buffer is allocated beyond its layout's `rows`:
 // the last tile's window (<= 8 waves x 96 byte rows, 16 x 24 bit rows) may

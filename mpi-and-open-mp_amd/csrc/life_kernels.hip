@@ -292,20 +292,21 @@ struct TArgs {
     // partitioned shard); workgroup b belongs to the region with first[k] <= b
     int64_t tx0[kMaxRegions], tx1[kMaxRegions], ty0[kMaxRegions], ty1[kMaxRegions], first[kMaxRegions + 1];
     int32_t nreg, m;  // generations of the launch = ghost rows at each end of a window (bit)
-    // banded tile column (bit; tile_geom): gsh < 6 cuts the tiles of column
-    // bcol into bands of G = 2^gsh lanes, 64 / G tile rows per workgroup; a
-    // region whose tx1 == bcol + 1 lists its full tiles first, then its
-    // ceil((ty1 - ty0) / (64 / G)) banded items
-    int32_t gsh;
-    int64_t bcol;
+    // banded tile column (bit; tile_geom): nband > 0 cuts the tiles of the
+    // last tile column (tile columns [.., btx1) end with it) into nband
+    // sub-columns; sub-column i owns pairs [borg[i], borg[i] + bown[i]) in
+    // bands of G = 2^bgsh[i] lanes, 64 / G tile rows per workgroup.  A region
+    // whose tx1 == btx1 lists its full tiles first, then the ceil((ty1 -
+    // ty0) / (64 / G)) banded items of sub-column 0, then those of 1
+    int32_t nband, bgsh[kMaxBands], bown[kMaxBands];
+    int64_t borg[kMaxBands], btx1;
     // tail split (bit, a launch of one region; launch_tstep): with tail_ntx
     // > 0, workgroups >= tail_first run half-height tiles (R / 2 rows per
     // wave) over owned rows [tail_y, tail_yend), tile columns [tail_tx0,
     // tail_tx0 + tail_ntx) per tile row, the last one banded like the full
-    // tiles when it is the banded column (tail_band), so the last round of a
-    // launch is made of half-length items
+    // tiles when it is the banded column (tail_tx0 + tail_ntx == btx1), so
+    // the last round of a launch is made of half-length items
     int64_t tail_first, tail_y, tail_yend, tail_ntx, tail_tx0;
-    int32_t tail_band;
     // XCD-aware order (bit, LIFE_XCD_ORDER): workgroups [0, xcd_n) are
     // renumbered so that each XCD (blocks b, b + 8, ... share one) walks a
     // contiguous row-major run of items; 0: dispatch order
@@ -347,15 +348,19 @@ struct XchB {
 // stores (FLOW 1) or plain stores (FLOW 2, the kernel releases them with a
 // fence): the rows are another workgroup's output of the same launch.
 //
-// Banded tiles: a tile column that owns o <= 30 pairs (the last one: W =
-// 62 (ntx - 1) + o) wastes most of a 64-lane tile.  With gsh < 6 the wave is
-// cut into groups of G = 2^gsh lanes (1 ghost + o owned + ghost pairs), group
-// g holding tile row ty + g of that column: one workgroup carries nb <= 64 /
-// G tile rows ("bands").  The neighbour dwords a group's edge lanes fetch
-// come from the adjacent group: garbage, exactly as a tile's lanes 0 / 63
-// read beyond the tile, absorbed by the ghost lanes.  Only the loads and
-// stores differ (per-lane rows); the generation loop is the tile's.  gsh = 6:
-// an ordinary tile (nb = 1).
+// Banded tiles: a tile column that owns o < 62 pairs (the last one: W =
+// 62 (ntx - 1) + o) wastes part of a 64-lane tile.  BAND: the wave is cut
+// into groups of G = 2^gsh lanes (1 ghost + own owned + ghost pairs), group
+// g holding tile row ty + g of pairs [org, org + own): one workgroup carries
+// nb <= 64 / G tile rows ("bands").  The neighbour dwords a group's edge
+// lanes fetch come from the adjacent group: garbage, exactly as a tile's
+// lanes 0 / 63 read beyond the tile, absorbed by the ghost lanes.  Only the
+// loads and stores differ (per-lane rows); the generation loop is the tile's.
+// The column may run as two such sub-columns (life::band_split; 65536^2: o =
+// 32 as 30 pairs at G = 32 and 2 at G = 4, 36 lanes per tile row instead of
+// 64): each is a narrow tile column of its own, whose ghost lanes load the
+// other's edge pair from the input buffer.  Without BAND: an ordinary tile
+// (gsh = 6, nb = 1).
 // LIFE_FLOW_BP_AHEAD (default 1): the dataflow tiles' generation loop issues
 // each row's two neighbour permutes that many rows ahead of their use, rows
 // fenced in program order.  Left to itself the compiler scheduled that loop
@@ -380,7 +385,7 @@ struct XchB {
 template <int R, bool WRAPX, bool WRAPY, int FLOW, int NW, bool BAND = false>
 __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in, uint8_t *out, int64_t tx,
                                               int64_t ty, XchB<NW> &xb, int gsh = 6, int nb = 1,
-                                              int64_t ybase = 0, int64_t yend = -1) {
+                                              int64_t ybase = 0, int64_t yend = -1, int64_t org = 0, int own = 62) {
     XchP<NW> &xch = xb.s;
     static_assert(R >= 3, "window");
     const int K = a.m;  // ghost rows per window end
@@ -391,7 +396,8 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
     const int wi = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int gl = BAND ? lane >> gsh : 0;                  // this lane's band (tile row ty + gl)
     const int pin = BAND ? lane & ((1 << gsh) - 1) : lane;  // lane within its group
-    const int64_t j = tx * 62 + pin - 1;                    // pair column of this lane
+    // pair column of this lane (BAND: the sub-column's pairs start at org; tx is not used)
+    const int64_t j = (BAND ? org : tx * 62) + pin - 1;
     int64_t jl;
     if (WRAPX) {
         // j lies in [-1, W + 62): one conditional add / subtract when W >= 64
@@ -551,8 +557,8 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
     asm volatile("" : "+v"(lane2));
     const int gl2 = BAND ? lane2 >> gsh : 0;
     const int pin2 = BAND ? lane2 & ((1 << gsh) - 1) : lane2;
-    const int64_t j2 = tx * 62 + pin2 - 1;
-    const bool st = (BAND ? (pin2 >= 1 && pin2 <= (1 << gsh) - 2 && j2 < a.W && gl2 < nb)
+    const int64_t j2 = (BAND ? org : tx * 62) + pin2 - 1;
+    const bool st = (BAND ? (pin2 >= 1 && pin2 <= own && gl2 < nb)
                           : (lane2 >= 1 && lane2 <= 62 && j2 < a.W)) ||
                     (!WRAPX && a.xext && (!BAND || gl2 < nb) && (j2 == -1 || j2 == a.W));
     const int64_t yb = y0 + (BAND ? (int64_t)(gl2 < nb ? gl2 : 0) * T : 0);  // this lane's band
@@ -739,27 +745,40 @@ __device__ __forceinline__ void tile_body_byte(const TArgs &a, const uint8_t *in
 // (R = 16) or 1 at 128.
 constexpr int bit_wpe(int NW, int R) { return NW == 16 ? (R <= 16 ? 8 : 4) : (R <= 24 ? 6 : 4); }
 
+// Banded item i of a region's last tile column: tile rows [ty0, ty0 + rows)
+// as the items of sub-column 0 (ceil(rows / B_0), B_i = 64 >> bgsh[i] tile
+// rows each), then those of sub-column 1.  Wave-uniform throughout.
+template <int RS, bool WRAPX, bool WRAPY, int NW>
+__device__ __forceinline__ void band_item(const TArgs &a, int64_t i, int64_t ty0, int64_t rows, XchB<NW> &xch,
+                                          int64_t ybase = 0, int64_t yend = -1) {
+    const int64_t n0 = (rows + (64 >> a.bgsh[0]) - 1) >> (6 - a.bgsh[0]);
+    const bool second = a.nband > 1 && i >= n0;
+    if (second) i -= n0;
+    const int gsh = second ? a.bgsh[1] : a.bgsh[0], own = second ? a.bown[1] : a.bown[0];
+    const int64_t org = second ? a.borg[1] : a.borg[0];
+    const int64_t B = 64 >> gsh, t = i * B;  // first tile row of the item within the region
+    const int nb = (int)(rows - t < B ? rows - t : B);
+    tile_body_bit<RS, WRAPX, WRAPY, 0, NW, true>(a, a.in, a.out, 0, ty0 + t, xch, gsh, nb, ybase, yend, org, own);
+}
+
 // Item i of the tail (TArgs::tail_*): RS rows per wave, tile rows of TS =
 // NW RS - 2m owned rows from owned row tail_y, the last one stopping at
 // tail_yend; tail_ntx - 1 ordinary tiles per tile row from column tail_tx0,
-// then the banded items of the last tile column (B = 64 >> gsh tile rows
-// each), or tail_ntx tiles per row without it.  (Round 5's half tiles spanned
+// then the banded items of the last tile column (band_item), or tail_ntx
+// tiles per row without it.  (Round 5's half tiles spanned
 // the last column as full-width tiles; banded they take (64 - o - 2) / 64
 // fewer lanes there.)
 template <int RS, bool WRAPX, bool WRAPY, int NW>
 __device__ __forceinline__ void tail_item(const TArgs &a, int64_t i, XchB<NW> &xch) {
     const int64_t TS = (int64_t)NW * RS - 2 * a.m, y0 = a.tail_y, yend = a.tail_yend;
     const int64_t rows = (yend - y0 + TS - 1) / TS;
-    const bool band = a.tail_band != 0;
+    const bool band = a.nband > 0 && a.tail_tx0 + a.tail_ntx == a.btx1;
     const int64_t ntxs = a.tail_ntx - (band ? 1 : 0), nfull = ntxs * rows;
-    if (i < nfull) {
+    if (i < nfull)
         tile_body_bit<RS, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, a.tail_tx0 + i % ntxs, i / ntxs, xch, 6, 1, y0,
                                               yend);
-    } else {
-        const int64_t B = 64 >> a.gsh, ty = (i - nfull) * B;
-        const int nb = (int)(rows - ty < B ? rows - ty : B);
-        tile_body_bit<RS, WRAPX, WRAPY, 0, NW, true>(a, a.in, a.out, a.bcol, ty, xch, a.gsh, nb, y0, yend);
-    }
+    else
+        band_item<RS, WRAPX, WRAPY, NW>(a, i - nfull, 0, rows, xch, y0, yend);
 }
 
 // One workgroup per tile (or banded item / partial-height tail tile).
@@ -786,16 +805,14 @@ __global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tstep_bit_kernel(TArg
     int k = 0;
     while (k + 1 < a.nreg && wg >= a.first[k + 1]) ++k;
     const int64_t wr = wg - a.first[k];
-    const bool bands = a.gsh < 6 && a.tx1[k] == a.bcol + 1;
+    const bool bands = a.nband > 0 && a.tx1[k] == a.btx1;
     const int64_t ntx = a.tx1[k] - a.tx0[k] - (bands ? 1 : 0);
     const int64_t nfull = ntx * (a.ty1[k] - a.ty0[k]);
     if (wr < nfull) {
         const int64_t tx = a.tx0[k] + wr % ntx, ty = a.ty0[k] + wr / ntx;
         tile_body_bit<R, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, tx, ty, xch);
     } else {
-        const int64_t B = 64 >> a.gsh, ty = a.ty0[k] + (wr - nfull) * B;
-        const int nb = (int)(a.ty1[k] - ty < B ? a.ty1[k] - ty : B);
-        tile_body_bit<R, WRAPX, WRAPY, 0, NW, true>(a, a.in, a.out, a.bcol, ty, xch, a.gsh, nb);
+        band_item<R, WRAPX, WRAPY, NW>(a, wr - nfull, a.ty0[k], a.ty1[k] - a.ty0[k], xch);
     }
     wg_trace(1);
 }
@@ -838,9 +855,10 @@ __global__ __launch_bounds__(64 * NW, LIFE_BYTE_WPE) void tstep_byte_kernel(TArg
 struct FArgs {
     TArgs t;                         // geometry, m; t.in / t.out: buffers of pass 0
     int64_t ntx, nty, items;         // items = passes * per_pass
-    // BAND: the last tile column (t.bcol) as banded items of B = 64 >> t.gsh
-    // tile rows; a pass is ngroups groups of B tile rows, each (ntx - 1) * B
-    // ordinary items then one banded item (tile rows past nty: no-op items)
+    // BAND: the last tile column (t.btx1 - 1; one sub-column) as banded items
+    // of B = 64 >> t.bgsh[0] tile rows; a pass is ngroups groups of B tile
+    // rows, each (ntx - 1) * B ordinary items then one banded item (tile rows
+    // past nty: no-op items)
     int64_t per_pass, ngroups, B;
     unsigned int *head;              // queue head (zeroed before the launch), then an error word: 1 + the
                                      // last item whose dependency wait timed out (0: none)
@@ -918,7 +936,7 @@ __global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tflow_kernel(FArgs f)
                 tx = off % nfull;
                 ty = ty0 + off / nfull;
             } else {
-                tx = a.bcol;
+                tx = a.btx1 - 1;
                 ty = ty0;
                 nb = (int)(f.nty - ty0 < f.B ? f.nty - ty0 : f.B);
             }
@@ -962,8 +980,9 @@ __global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tflow_kernel(FArgs f)
         if (LIFE_WG_TRACE && traced < 4) wg_trace(2 + 3 * traced);
         const uint8_t *in = (p & 1) ? a.out : a.in;
         uint8_t *out = const_cast<uint8_t *>((p & 1) ? a.in : a.out);
-        if (BAND && tx == a.bcol)
-            tile_body_bit<R, WRAPX, WRAPY, FLOW, NW, true>(a, in, out, tx, ty, xch, a.gsh, nb);
+        if (BAND && tx == a.btx1 - 1)
+            tile_body_bit<R, WRAPX, WRAPY, FLOW, NW, true>(a, in, out, tx, ty, xch, a.bgsh[0], nb, 0, -1, a.borg[0],
+                                                           a.bown[0]);
         else
             tile_body_bit<R, WRAPX, WRAPY, FLOW, NW>(a, in, out, tx, ty, xch);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have left
@@ -1460,7 +1479,10 @@ int tile_ghost(const life_layout &L, int m) {
 // LIFE_BANDS=0: no banded tile column (A/B knob)
 static bool bands_enabled() { static const bool on = env::read(env::kBands) != 0; return on; }
 
-TileGeom tile_geom(const life_layout &L, int m) {
+// LIFE_BAND_SPLIT=0: at most one sub-column, the rule before the split (A/B knob)
+static bool band_split_enabled() { static const bool on = env::read(env::kBandSplit) != 0; return on; }
+
+TileGeom tile_geom(const life_layout &L, int m, bool one_band) {
     TileGeom g;
     const bool bit = is_bit(L);
     g.lanes = 62;
@@ -1469,13 +1491,16 @@ TileGeom tile_geom(const life_layout &L, int m) {
     const int64_t W = (L.w + g.cells - 1) / g.cells;  // lane columns (pairs / words) per row
     g.ntx = (W + g.lanes - 1) / g.lanes;
     g.nty = (L.h + g.rows - 1) / g.rows;
-    // the last tile column owns o lane columns: bands of G >= o + 2 lanes when
-    // G <= 32 (65536^2: 1024 pairs, o = 32, no bands; 32768^2: o = 16, G = 32)
+    // the last tile column owns o lane columns, run as the sub-columns of
+    // life::band_split (65536^2: 1024 pairs, o = 32, {30, G 32} + {2, G 4};
+    // 32768^2: o = 16, {14, G 16} + {2, G 4}).  One band: G >= o + 2 lanes
+    // when G <= 32 (o = 32: a whole tile, o = 16: G = 32)
     const int64_t o = W - g.lanes * (g.ntx - 1);
-    int gsh = 2;
-    while ((1 << gsh) < o + 2) ++gsh;
-    g.gsh = bit && bands_enabled() && gsh <= 5 ? gsh : 6;
-    g.bcol = g.gsh < 6 ? g.ntx - 1 : -1;
+    const bool split = !one_band && band_split_enabled();
+    const BandSplit sp = bit && bands_enabled() ? band_split(o, split ? kMaxBands : 1) : BandSplit{};
+    g.nband = sp.n;
+    for (int i = 0; i < kMaxBands; i++) g.band[i] = sp.b[i];
+    g.bcol = g.nband > 0 ? g.ntx - 1 : -1;
     return g;
 }
 
@@ -1536,9 +1561,15 @@ int tile_slots(const life_layout &L) {
 
 int64_t region_items(const TileGeom &g, const TileRegion &r) {
     if (r.tx1 <= r.tx0 || r.ty1 <= r.ty0) return 0;
-    if (g.gsh >= 6 || r.tx1 != g.bcol + 1) return (r.tx1 - r.tx0) * (r.ty1 - r.ty0);
-    const int64_t B = 64 >> g.gsh;
-    return (r.tx1 - r.tx0 - 1) * (r.ty1 - r.ty0) + (r.ty1 - r.ty0 + B - 1) / B;
+    const BandRows b = region_bands(g, r.tx1);
+    return tail_row_items(r.tx1 - r.tx0 - (b.n > 0 ? 1 : 0), b, r.ty1 - r.ty0);
+}
+
+BandRows region_bands(const TileGeom &g, int64_t tx1) {
+    BandRows b;
+    if (g.nband > 0 && tx1 == g.bcol + 1)
+        for (b.n = 0; b.n < g.nband; b.n++) b.B[b.n] = 64 >> g.band[b.n].gsh;
+    return b;
 }
 
 life_layout extended_layout(const life_layout &L, const Extend &ext) {
@@ -1549,10 +1580,6 @@ life_layout extended_layout(const life_layout &L, const Extend &ext) {
     return V;
 }
 
-// Bands of the tile columns [tx0, tx1): B tile rows per banded item when
-// the region holds the banded last column, else 1 (no bands).
-static int64_t region_bands(const TileGeom &g, int64_t tx1) { return g.gsh < 6 && tx1 == g.bcol + 1 ? 64 >> g.gsh : 1; }
-
 // The tail plan of a bit launch over tile columns [tx0, tx1) x rows [ty0,
 // ty1) of tile_geom(L, m), beside `pre` items of another launch dispatched
 // just before it (launch_tstep; cached by life::tail_plan).
@@ -1560,7 +1587,8 @@ static TailPlan tail_plan_for(const life_layout &L, const TileGeom &g, int m, in
                               int64_t ty1, int64_t pre) {
     const int64_t T2 = (int64_t)tile_waves(true) * (temporal_rows(true) / 2) - 2 * (int64_t)tile_ghost(L, m);
     const int64_t yend = std::min(ty1 * g.rows, L.h);
-    return tail_plan(tx1 - tx0, region_bands(g, tx1), ty0, ty1, yend, g.rows, T2, tstep_bit_slots(),
+    const BandRows b = region_bands(g, tx1);
+    return tail_plan(tx1 - tx0 - (b.n > 0 ? 1 : 0), b, ty0, ty1, yend, g.rows, T2, tstep_bit_slots(),
                      tail_split_mode(), kTailC, pre);
 }
 
@@ -1575,6 +1603,18 @@ void prewarm_tail_plans(const life_layout &L, int mmax, bool ext_y) {
             const TileGeom g = tile_geom(V, m);
             if (g.rows >= 1) (void)tail_plan_for(V, g, m, 0, g.ntx, 0, g.nty, 0);
         }
+}
+
+// the banded column of g as the kernels take it (none: nband = 0)
+static void set_bands(TArgs &a, const TileGeom &g) {
+    a.nband = (int32_t)g.nband;
+    a.btx1 = g.bcol + 1;
+    for (int i = 0; i < kMaxBands; i++) {
+        const bool on = i < g.nband;
+        a.bgsh[i] = on ? g.band[i].gsh : 6;
+        a.bown[i] = on ? g.band[i].own : 0;
+        a.borg[i] = on ? g.bcol * g.lanes + g.band[i].first : 0;
+    }
 }
 
 hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out, const TileRegion *r, int nreg,
@@ -1604,8 +1644,7 @@ hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out,
     a.xext = ext.x ? 1 : 0;
     a.nreg = 0;
     a.first[0] = 0;
-    a.gsh = (int32_t)g.gsh;
-    a.bcol = g.bcol;
+    set_bands(a, g);
     for (int k = 0; k < nreg; k++) {
         if (r[k].tx1 <= r[k].tx0 || r[k].ty1 <= r[k].ty0) continue;
         const int n = a.nreg++;
@@ -1618,7 +1657,6 @@ hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out,
     if (a.nreg == 0 || m <= 0) return hipSuccess;
     int64_t items = a.first[a.nreg];  // one workgroup per tile (or banded item)
     a.tail_first = a.tail_y = a.tail_yend = a.tail_ntx = a.tail_tx0 = 0;
-    a.tail_band = 0;
     const int64_t T2 = (int64_t)tile_waves(bit) * (temporal_rows(bit) / 2) - 2 * (int64_t)tile_ghost(L, m);
     if (bit && T2 >= 1 && a.nreg == 1 && tail_split_mode() > 0 && concurrent >= 0) {
         // One region: the whole shard, a deep-halo pass over the extended
@@ -1633,7 +1671,8 @@ hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out,
         // (2 per CU, 32 ghost rows: a third of a half tile) lost 3-4 % with
         // half tiles (profiles/r02/r2z) and keep whole tiles.
         const int64_t tx0 = a.tx0[0], tx1 = a.tx1[0], ty0 = a.ty0[0], ty1 = a.ty1[0];
-        const int64_t yend = std::min(ty1 * g.rows, L.h), B = region_bands(g, tx1);
+        const int64_t yend = std::min(ty1 * g.rows, L.h);
+        const BandRows bands = region_bands(g, tx1);
         const TailPlan p = tail_plan_for(L, g, m, tx0, tx1, ty0, ty1, concurrent);
         if (p.F < ty1 && p.F >= ty0) {
             a.ty1[0] = p.F;
@@ -1643,8 +1682,7 @@ hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out,
             a.tail_yend = yend;
             a.tail_ntx = tx1 - tx0;
             a.tail_tx0 = tx0;
-            a.tail_band = B > 1 ? 1 : 0;
-            items = a.tail_first + tail_row_items(tx1 - tx0, B, p.n2);
+            items = a.tail_first + tail_row_items(tx1 - tx0 - (bands.n > 0 ? 1 : 0), bands, p.n2);
         }
     }
     const bool split = a.tail_ntx > 0;
@@ -1684,13 +1722,15 @@ const void *flow_kernel_of(const life_layout &L, int flow, bool band = false) {
     return nullptr;
 }
 // the banded form for this geometry: a banded last column (tile_geom)
-bool flow_band(const TileGeom &g) { return g.gsh < 6 && flow_bands_enabled(); }
+bool flow_band(const TileGeom &g) { return g.nband > 0 && flow_bands_enabled(); }
+// the dataflow form's geometry: one band at most (tile_geom's one_band mode)
+TileGeom flow_geom(const life_layout &L, int m) { return tile_geom(L, m, true); }
 }  // namespace
 
 int64_t flow_items_per_pass(const life_layout &L, int m, bool work_only) {
-    const TileGeom g = tile_geom(L, m);
+    const TileGeom g = flow_geom(L, m);
     if (!flow_band(g)) return g.ntx * g.nty;
-    const int64_t B = 64 >> g.gsh, ngroups = (g.nty + B - 1) / B;
+    const int64_t B = 64 >> g.band[0].gsh, ngroups = (g.nty + B - 1) / B;
     // work_only: without the no-op padding items of the last group
     return work_only ? (g.ntx - 1) * g.nty + ngroups : ngroups * ((g.ntx - 1) * B + 1);
 }
@@ -1700,7 +1740,7 @@ bool flow_ok(const life_layout &L, int m) {
     // reads tile rows ty-2..ty+2: a window may reach at most one tile row
     // beyond its neighbours (ghost rows <= T)
     if (!flow_kernel_of(L, 1) || m < 1) return false;
-    const TileGeom g = tile_geom(L, m);
+    const TileGeom g = flow_geom(L, m);
     return g.rows >= tile_ghost(L, m);
 }
 
@@ -1715,7 +1755,7 @@ int flow_slots(const life_layout &L) {
 }
 
 hipError_t prewarm_tflow(const life_layout &L, int m, int flow, unsigned int *head, hipStream_t s) {
-    const TileGeom g = tile_geom(L, m);
+    const TileGeom g = flow_geom(L, m);
     const void *fn = flow_kernel_of(L, flow, flow_band(g));
     if (!fn || !flow_ok(L, m) || flow_slots(L) <= 0) return hipErrorInvalidValue;  // (caches the slot count)
     FArgs f{};  // no items: the one workgroup pulls item 0 and leaves
@@ -1732,7 +1772,7 @@ hipError_t launch_tflow(const life_layout &L, const uint8_t *in, uint8_t *out, i
     if (!fn || !wrap.x || !wrap.y || m < 1 || m > 32 || m > L.generations_per_exchange || passes < 1 ||
         !flow_ok(L, m))
         return hipErrorInvalidValue;
-    const TileGeom g = tile_geom(L, m);
+    const TileGeom g = flow_geom(L, m);
     FArgs f{};
     f.t.in = in;
     f.t.out = out;
@@ -1744,11 +1784,12 @@ hipError_t launch_tflow(const life_layout &L, const uint8_t *in, uint8_t *out, i
     f.t.m = m;
     const bool band = flow_band(g);
     if (band) fn = flow_kernel_of(L, flow, true);
-    f.t.gsh = band ? (int32_t)g.gsh : 6;
-    f.t.bcol = band ? g.bcol : -1;
+    TileGeom gb = g;
+    if (!band) gb.nband = 0, gb.bcol = -1;
+    set_bands(f.t, gb);
     f.ntx = g.ntx;
     f.nty = g.nty;
-    f.B = band ? 64 >> g.gsh : 1;
+    f.B = band ? 64 >> g.band[0].gsh : 1;
     f.ngroups = (g.nty + f.B - 1) / f.B;
     f.per_pass = flow_items_per_pass(L, m);
     f.items = passes * f.per_pass;

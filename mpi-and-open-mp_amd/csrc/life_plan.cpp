@@ -423,43 +423,97 @@ struct SlotGroups {
 };
 
 struct TailKey {
-    int64_t ntx, B, ty0, ty1, yend, T, T2, slots, pre;
-    int mode;
+    int64_t nfull, B0, B1, ty0, ty1, yend, T, T2, slots, pre;
+    int nb, mode;
     double c;
     bool operator==(const TailKey &o) const {
-        return ntx == o.ntx && B == o.B && ty0 == o.ty0 && ty1 == o.ty1 && yend == o.yend && T == o.T && T2 == o.T2 &&
-               slots == o.slots && pre == o.pre && mode == o.mode && c == o.c;
+        return nfull == o.nfull && nb == o.nb && B0 == o.B0 && B1 == o.B1 && ty0 == o.ty0 && ty1 == o.ty1 &&
+               yend == o.yend && T == o.T && T2 == o.T2 && slots == o.slots && pre == o.pre && mode == o.mode &&
+               c == o.c;
     }
 };
+// the one-band forms' column count and band as a band list
+int64_t one_band_full(int64_t ntx, int64_t B) { return B > 1 ? ntx - 1 : ntx; }
+life::BandRows one_band(int64_t B) {
+    life::BandRows b;
+    if (B > 1) {
+        b.n = 1;
+        b.B[0] = B;
+    }
+    return b;
+}
 }  // namespace
+
+life::BandSplit life::band_split(int64_t o, int max_parts) {
+    BandSplit s;
+    if (o < 1 || o > 62) return s;
+    // lanes of the smallest group holding x owned pairs (x <= 30)
+    auto gsh_of = [](int64_t x) {
+        int g = 2;
+        while ((1 << g) < x + 2) ++g;
+        return g;
+    };
+    int best = 64;  // a whole tile
+    if (o <= 30) {
+        s.n = 1;
+        s.b[0] = BandCol{0, (int)o, gsh_of(o)};
+        best = 1 << s.b[0].gsh;
+    }
+    // two parts {a, o - a}: strictly fewer lanes only, the widest first part first
+    for (int64_t a = std::min<int64_t>(o - 1, 30); max_parts > 1 && a >= 1 && o - a <= 30; --a) {
+        const int g0 = gsh_of(a), g1 = gsh_of(o - a), lanes = (1 << g0) + (1 << g1);
+        if (lanes >= best) continue;
+        best = lanes;
+        s.n = 2;
+        s.b[0] = BandCol{0, (int)a, g0};
+        s.b[1] = BandCol{(int)a, (int)(o - a), g1};
+    }
+    return s;
+}
 
 double life::tail_makespan2(int64_t ntx, int64_t B, int64_t F_rows, int64_t n2, int64_t slots, double c,
                             int64_t pre) {
+    return tail_makespan2(one_band_full(ntx, B), one_band(B), F_rows, n2, slots, c, pre);
+}
+
+life::TailPlan life::tail_plan(int64_t ntx, int64_t B, int64_t ty0, int64_t ty1, int64_t yend, int64_t T,
+                               int64_t T2, int64_t slots, int mode, double c, int64_t pre) {
+    if (ntx < 1) {
+        TailPlan none;
+        none.F = ty1;
+        return none;
+    }
+    return tail_plan(one_band_full(ntx, B), one_band(B), ty0, ty1, yend, T, T2, slots, mode, c, pre);
+}
+
+double life::tail_makespan2(int64_t nfull, const BandRows &bands, int64_t F_rows, int64_t n2, int64_t slots,
+                            double c, int64_t pre) {
     if (slots < 1) return 0.0;
-    const int64_t nf = (pre > 0 ? pre : 0) + tail_row_items(ntx, B, F_rows);
+    const int64_t nf = (pre > 0 ? pre : 0) + tail_row_items(nfull, bands, F_rows);
     const int64_t r = nf / slots, rem = nf % slots;
     SlotGroups g;
     g.add((double)r, slots - rem);
     if (rem) g.add((double)(r + 1), rem);
     const double end = nf ? (double)(r + (rem ? 1 : 0)) : 0.0;
-    return g.deal(c + (1.0 - c) * 0.5, tail_row_items(ntx, B, n2), end);
+    return g.deal(c + (1.0 - c) * 0.5, tail_row_items(nfull, bands, n2), end);
 }
 
-life::TailPlan life::tail_plan(int64_t ntx, int64_t B, int64_t ty0, int64_t ty1, int64_t yend, int64_t T,
-                               int64_t T2, int64_t slots, int mode, double c, int64_t pre) {
+life::TailPlan life::tail_plan(int64_t nfull, const BandRows &bands, int64_t ty0, int64_t ty1, int64_t yend,
+                               int64_t T, int64_t T2, int64_t slots, int mode, double c, int64_t pre) {
     TailPlan none;
     none.F = ty1;
-    if (ntx < 1 || ty1 <= ty0 || T < 1 || T2 < 1 || slots < 1 || mode < 1 || mode > 2 || pre < 0) return none;
+    if (nfull < 0 || nfull + bands.n < 1 || bands.n < 0 || bands.n > kMaxBands || ty1 <= ty0 || T < 1 || T2 < 1 || slots < 1 || mode < 1 || mode > 2 || pre < 0) return none;
     // the launch shares the slots with `pre` items dispatched before it
-    const int64_t nall = pre + tail_row_items(ntx, B, ty1 - ty0);
-    none.makespan = tail_makespan2(ntx, B, ty1 - ty0, 0, slots, c, pre);
+    const int64_t nall = pre + tail_row_items(nfull, bands, ty1 - ty0);
+    none.makespan = tail_makespan2(nfull, bands, ty1 - ty0, 0, slots, c, pre);
     // Whole rounds: nothing to fill.  One round or less: the model's slots are
     // not independent there (a CU's three slots share its SIMDs, and a lone
     // tile runs faster), so it is not trusted to re-tile an underfilled launch.
     if (nall <= slots || nall % slots == 0) return none;
     static std::mutex mu;
     static std::vector<std::pair<TailKey, TailPlan>> cache;
-    const TailKey key{ntx, B, ty0, ty1, yend, T, T2, slots, pre, mode, c};
+    const TailKey key{nfull, bands.n > 0 ? bands.B[0] : 1, bands.n > 1 ? bands.B[1] : 1, ty0, ty1, yend, T, T2, slots, pre,
+                      bands.n, mode, c};
     {
         std::lock_guard<std::mutex> lk(mu);
         for (const auto &e : cache)
@@ -475,18 +529,18 @@ life::TailPlan life::tail_plan(int64_t ntx, int64_t B, int64_t ty0, int64_t ty1,
         // round, when the last round is under half full
         if (nall % slots <= slots / 2) {
             int64_t q = 1;
-            while (q < ty1 - ty0 && tail_row_items(ntx, B, (q * T + T2 - 1) / T2) < slots) ++q;
+            while (q < ty1 - ty0 && tail_row_items(nfull, bands, (q * T + T2 - 1) / T2) < slots) ++q;
             if (q < ty1 - ty0) {
                 best.F = ty1 - q;
                 best.n2 = halves(best.F);
-                best.makespan = tail_makespan2(ntx, B, best.F - ty0, best.n2, slots, c, pre);
+                best.makespan = tail_makespan2(nfull, bands, best.F - ty0, best.n2, slots, c, pre);
             }
         }
     } else {
         // every split point (ties keep more full tiles)
         for (int64_t F = ty1 - 1; F >= ty0; --F) {
             const int64_t n2 = halves(F);
-            const double t = tail_makespan2(ntx, B, F - ty0, n2, slots, c, pre);
+            const double t = tail_makespan2(nfull, bands, F - ty0, n2, slots, c, pre);
             if (t < best.makespan - 1e-9) {
                 best.F = F;
                 best.n2 = n2;

@@ -98,7 +98,8 @@ constexpr int kPipeAutoRegions = 4;
 constexpr double kPipeAutoRounds = 1.0;
 constexpr int64_t kPipeAutoPasses = 4;
 
-int64_t tile_bands(const life::TileGeom &g) { return g.gsh < 6 ? 64 >> g.gsh : 1; }
+// the banded items' tile rows of a whole-width region (regions align on the largest)
+life::BandRows tile_bands(const life::TileGeom &g) { return life::region_bands(g, g.ntx); }
 
 // stream2 starts after everything queued on stream / stream after everything on stream2
 int fence_stream2(Shard &s) {
