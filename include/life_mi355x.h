@@ -137,6 +137,21 @@ typedef struct {
 int life_layout_query(int64_t nx, int64_t ny, int dims0, int dims1, int rank, int kernel,
                       life_layout *out);
 
+/* Life-like (outer-totalistic) rules.  A rule is two 9-bit masks: `birth`
+ * bit k set = a dead cell with k live neighbours (of 8) is born, `survive`
+ * bit k set = a live cell with k live neighbours stays alive; every other cell
+ * is dead in the next generation.  Conway's B3/S23 (life_cart.c:202-208) is
+ * birth = 1 << 3, survive = (1 << 2) | (1 << 3).  life_rule_parse accepts
+ * "B36/S23" in either letter case and Golly's "23/3" (S/B): digits 0-8 in any
+ * order, repeats harmless, empty lists allowed ("B2/S"); anything else is
+ * LIFE_EINVAL with a life_last_error() message that quotes the text.
+ * life_rule_format writes the canonical "B.../S..." with ascending digits
+ * (LIFE_EINVAL for bits above 8).  Neither needs a GPU. */
+#define LIFE_RULE_CONWAY_BIRTH 0x008u
+#define LIFE_RULE_CONWAY_SURVIVE 0x00Cu
+int life_rule_parse(const char *text, uint32_t *birth, uint32_t *survive);
+int life_rule_format(uint32_t birth, uint32_t survive, char out[24]);
+
 const char *life_strerror(int err);
 const char *life_dev_strerror(int err); /* the same (SURVEY 8(b)'s name for it) */
 const char *life_last_error(void); /* detail of the last LIFE_EHIP/ERCCL on this thread */
@@ -353,7 +368,11 @@ int life_dev_set_timing(life_dev *d, int on);
  * when a pass is under 5 rounds of resident workgroups (its launch tail
  * would idle the chip: 32768^2), else off (65536^2, where the per-launch
  * tiles measured 3 % faster).  The byte encoding always runs
- * per-launch tiles.  Same results. */
+ * per-launch tiles.  Same results.  Neither this option nor
+ * LIFE_OPT_SMALL_GRID applies while a rule other than B3/S23 is set
+ * (life_dev_set_rule): the dataflow and small-grid kernels exist for B3/S23
+ * only, and those calls run the per-launch tiles or the one-generation
+ * kernel. */
 #define LIFE_OPT_FLOW 7
 /* LIFE_OPT_FLOW_CHUNK (default 0 = automatic): the dataflow launch's queue
  * head is a 32-bit counter, so a step call's passes are split over several
@@ -394,6 +413,29 @@ int life_dev_set_timing(life_dev *d, int on);
  * Same results; the statistics count one launch per pass either way. */
 #define LIFE_OPT_PIPELINE 11
 int life_dev_configure(life_dev *d, int option, int value);
+/* The rule the device evolves under (masks as life_rule_parse gives them); a
+ * new device runs B3/S23.  life_dev_set_rule waits for queued work, as
+ * life_dev_configure does, and may be called between any two step calls; the
+ * state is untouched.  LIFE_EINVAL, with a message, for: bits above 8;
+ * birth & 1 (B0 rules: the tiles' zero slots above and below the window, the
+ * allocation slack rows and the row padding all rely on "nothing is born from
+ * nothing" -- lifting that is out of scope); any rule other than B3/S23 on a
+ * LIFE_KERNEL_BYTE device (the byte encoding is the reference-layout
+ * comparison, its kernels SWAR arithmetic on byte sums: rules are a feature of
+ * the bit encoding).  In rank mode (world > 1) the call is COLLECTIVE and
+ * checks with the all-reduce of LIFE_OPT_DEEP_HALO that every rank passes the
+ * same rule (never executed with world > 1: one-GPU boxes).
+ * Paths under a rule other than B3/S23: the per-launch bit tiles in every
+ * launch form (whole block, ring / interior, deep-halo passes, banded
+ * columns, half-height tail, pipelined regions) and the one-generation bit
+ * kernel run the rule as a compile-time variant of the same code (the table
+ * tail: 25 instead of 12 bit operations per dword, 2 tiles per CU instead of
+ * 3); LIFE_OPT_FLOW and LIFE_OPT_SMALL_GRID are ignored while such a rule is
+ * set -- those shapes run the tiles or the one-generation kernel, and
+ * life_dev_last_path reports what ran.  Setting B3/S23 again returns the
+ * device to the B3/S23 kernels and paths exactly. */
+int life_dev_set_rule(life_dev *d, uint32_t birth, uint32_t survive);
+int life_dev_get_rule(life_dev *d, uint32_t *birth, uint32_t *survive);
 /* The kernel family that ran the bulk of the last life_dev_step call:
  * LIFE_PATH_ONEGEN (one generation per launch), _TILES (temporally blocked
  * tiles, one launch per pass), _FLOW (the dataflow tiles, LIFE_OPT_FLOW),

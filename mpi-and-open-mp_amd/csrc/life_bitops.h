@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "life_host.h"
+
 namespace life {
 
 // v_bitop3_b32 (gfx950): any 3-input bitwise function in one VALU op.  The
@@ -121,6 +123,67 @@ struct BitEnc {
         return o;
     }
 };
+
+// Rule policies of the bit kernels' shared bodies (tile_body_bit, strip_full /
+// strip_tail): what turns three rows' 2-bit sums and the cell into its next
+// state.  A compile-time choice: the B3/S23 instances are the code they were
+// before the policy existed.
+struct ConwayRule {
+    static constexpr bool kTable = false;
+    __device__ __forceinline__ uint32_t operator()(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0,
+                                                   uint32_t c1, uint32_t alive) const {
+        return BitEnc::rule1(a0, a1, b0, b1, c0, c1, alive);
+    }
+};
+
+constexpr uint32_t kAndXor = ((0xF0 & 0xCC) ^ 0xAA) & 0xFF;  // (a & b) ^ c
+constexpr uint32_t kXor2 = (0xF0 ^ 0xCC) & 0xFF;              // a ^ b (c ignored)
+
+// Any outer-totalistic rule without B0 (life_dev_set_rule).  With n9 = u0 +
+// 2 S (the cell included, S = v0 + k0 + 2 v1 in 0..4) the next state is a
+// function of (alive, u0, S) that the rule's 18 bits decide: per (alive, S)
+// a leaf (u0 & A) ^ B of two lane-uniform all-ones / all-zeros words
+// (life::rule_words, life_plan.cpp; kept in VGPRs: a VOP3 op of gfx950 reads
+// one scalar source at most), five kMux on alive, and a select on S: v0 ^ k0
+// once, two 3-way selects (S = 0, 1, 2 and S = 2, 3, 4: v0 + k0 = 0, 1, 2 as
+// x ? L1 : (v0 ? L2 : L0)), one kMux on v1.  4 column-sum ops as B3/S23, then
+// 10 + 5 + 6 = 21: 25 VALU per dword against 12.
+struct TableRule {
+    static constexpr bool kTable = true;
+    uint32_t A[2][5], B[2][5];
+    __device__ __forceinline__ explicit TableRule(const RuleWords &w) {
+#pragma unroll
+        for (int q = 0; q < 10; ++q) {
+            A[q / 5][q % 5] = w.a[q / 5][q % 5];
+            B[q / 5][q % 5] = w.b[q / 5][q % 5];
+        }
+    }
+    __device__ __forceinline__ uint32_t operator()(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0,
+                                                   uint32_t c1, uint32_t alive) const {
+        const uint32_t u0 = b3<kXor3>(a0, b0, c0), k0 = b3<kMaj>(a0, b0, c0);
+        const uint32_t v0 = b3<kXor3>(a1, b1, c1), v1 = b3<kMaj>(a1, b1, c1);
+        uint32_t L[5];
+#pragma unroll
+        for (int s = 0; s < 5; ++s)
+            L[s] = b3<kMux>(alive, b3<kAndXor>(u0, A[1][s], B[1][s]), b3<kAndXor>(u0, A[0][s], B[0][s]));
+        const uint32_t x = b3<kXor2>(v0, k0, k0);
+        const uint32_t lo = b3<kMux>(x, L[1], b3<kMux>(v0, L[2], L[0]));
+        const uint32_t hi = b3<kMux>(x, L[3], b3<kMux>(v0, L[4], L[2]));
+        return b3<kMux>(v1, hi, lo);
+    }
+};
+
+// BitEnc::rule under a policy (the one-generation kernel's 16-B unit)
+template <class RP>
+__device__ __forceinline__ uint4 rule_unit(const RP &rp, const BitEnc::H &a, const BitEnc::H &b, const BitEnc::H &c,
+                                           uint4 v) {
+    uint4 o;
+    o.x = rp(a.s0[0], a.s1[0], b.s0[0], b.s1[0], c.s0[0], c.s1[0], v.x);
+    o.y = rp(a.s0[1], a.s1[1], b.s0[1], b.s1[1], c.s0[1], c.s1[1], v.y);
+    o.z = rp(a.s0[2], a.s1[2], b.s0[2], b.s1[2], c.s0[2], c.s1[2], v.z);
+    o.w = rp(a.s0[3], a.s1[3], b.s0[3], b.s1[3], c.s0[3], c.s1[3], v.w);
+    return o;
+}
 
 __device__ __forceinline__ uint32_t bperm(int addr, uint32_t v) {
     return (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)v);

@@ -227,7 +227,7 @@ void tail_prewarm(const life_dev *d) {
         bool seen = false;  // identical blocks share their plans (cached by shape)
         for (size_t j = 0; j < i; ++j)
             seen |= d->shards[j].lay.w == d->shards[i].lay.w && d->shards[j].lay.h == d->shards[i].lay.h;
-        if (!seen) life::prewarm_tail_plans(d->shards[i].lay, max_pass_gens(d), part(d, 1));
+        if (!seen) life::prewarm_tail_plans(d->shards[i].lay, max_pass_gens(d), part(d, 1), d->table);
     }
 }
 
@@ -569,6 +569,42 @@ int life_dev_configure(life_dev *d, int option, int value) {
     }
     default: return LIFE_EINVAL;
     }
+}
+
+int life_dev_set_rule(life_dev *d, uint32_t birth, uint32_t survive) {
+    if (!d) return LIFE_EINVAL;
+    CHK(life_dev_sync(d));
+    char name[24] = "";
+    if ((birth | survive) & ~life::kRuleMask) {
+        set_err("rule masks 0x%x / 0x%x: bits above 8", birth, survive);
+        return LIFE_EINVAL;
+    }
+    life::rule_format(birth, survive, name);
+    if (birth & 1u) {
+        set_err("rule %s: B0 rules are not supported (dead padding and ghost rows must stay dead)", name);
+        return LIFE_EINVAL;
+    }
+    const bool table = birth != life::kConwayBirth || survive != life::kConwaySurvive;
+    if (table && d->kernel != LIFE_KERNEL_BIT) {
+        set_err("rule %s: the byte encoding runs B3/S23 only (rules are a feature of LIFE_KERNEL_BIT)", name);
+        return LIFE_EINVAL;
+    }
+    // every rank must evolve the same universe: collective in rank mode, as LIFE_OPT_DEEP_HALO
+    if (d->rank_mode && d->world > 1) CHK(agree_all_ranks(d, (int)(birth | (survive << 9)), "life_dev_set_rule"));
+    d->birth = birth;
+    d->survive = survive;
+    const bool changed = table != d->table;
+    d->table = table;
+    if (table) d->words = life::rule_words(birth, survive);
+    if (changed) tail_prewarm(d);  // the tail plans of the kernel that will run (2 or 3 tiles per CU)
+    return LIFE_OK;
+}
+
+int life_dev_get_rule(life_dev *d, uint32_t *birth, uint32_t *survive) {
+    if (!d) return LIFE_EINVAL;
+    if (birth) *birth = d->birth;
+    if (survive) *survive = d->survive;
+    return LIFE_OK;
 }
 
 int life_tune(int kernel, int rows, int depth) {

@@ -137,6 +137,10 @@ struct life_dev {
     int flow = 0;  // LIFE_OPT_FLOW: single-shard bit tiles as one persistent dataflow launch per
                    // step call (1: write-through hand-off, 2: plain stores + release; 0 off; creation: LIFE_FLOW)
     int64_t flow_chunk = 0;  // LIFE_OPT_FLOW_CHUNK: passes per dataflow launch at most (0: automatic)
+    // life_dev_set_rule: the masks, and for a rule other than B3/S23 (`table`) the words its kernels take
+    uint32_t birth = life::kConwayBirth, survive = life::kConwaySurvive;
+    bool table = false;
+    life::RuleWords words{};
     int pipe = 0;  // LIFE_OPT_PIPELINE: 0 off, 1 automatic, R >= 3 regions whenever a plan exists (creation: LIFE_PIPELINE)
     // the current step call's pipelined passes (life_step.hip pipelined_pass): R = 0, none; the plan
     // and the pass count of the current run of passes of m generations (a new m: a new run)
@@ -170,6 +174,8 @@ namespace rt {
 inline bool part(const life_dev *d, int a) { return d->dims[a] > 1 || ((d->loop >> a) & 1); }
 // The shard wraps x itself (the x-apron is filled by launch_wrap_columns).
 inline bool self_wrap_x(const life_dev *d) { return !(d->loop & 1) && life::self_wrap_x(d->shards[0].lay, d->dims[0]); }
+// The table-rule kernels' words, null under B3/S23 (launch_step / launch_tstep).
+inline const life::RuleWords *rule_of(const life_dev *d) { return d->table ? &d->words : nullptr; }
 inline life::Wrap wrap_of(const life_dev *d) { return life::Wrap{!part(d, 0) && !self_wrap_x(d), !part(d, 1)}; }
 inline bool temporal(const life_dev *d) { return d->shards[0].lay.generations_per_exchange > 1; }
 // Deep halo applies (generation_block): bit tiles, a partitioned axis, no

@@ -117,6 +117,27 @@ inline PipePlan pipe_plan(int64_t nty, const BandRows &bands, int R, int S) {
 }
 #pragma GCC visibility pop
 
+// Life-like rules (life_rule_parse, life_dev_set_rule): `birth` bit k = a dead
+// cell with k live neighbours of 8 is born, `survive` bit k = a live cell
+// with k stays alive.  B3/S23 runs the hand-searched tail (BitEnc::rule1);
+// every other rule the table tail (TableRule, life_bitops.h), whose lane-
+// uniform words rule_words derives: with n9 the live cells of the 3 x 3 block,
+// the cell included, t(alive, n9) = birth bit n9 (dead; n9 = 9 cannot occur)
+// or survive bit n9 - 1 (alive; n9 = 0 cannot occur); for alive = 0 / 1 and S
+// = 0 .. 4 the leaf over n9 = 2 S + u0 is (u0 & a) ^ b with b = t(alive, 2 S)
+// and a = b ^ t(alive, 2 S + 1), each all-ones or zero.
+constexpr uint32_t kRuleMask = 0x1FFu, kConwayBirth = 1u << 3, kConwaySurvive = (1u << 2) | (1u << 3);
+struct RuleWords {
+    uint32_t a[2][5], b[2][5];  // [alive][S]
+};
+RuleWords rule_words(uint32_t birth, uint32_t survive);
+// The text forms: B36/S23 (either letter case) and Golly's 23/3 (S/B);
+// digits 0-8 in any order, repeats and empty lists allowed.  false: not a
+// rulestring.  rule_format writes the canonical B.../S... with ascending digits
+// (at most 22 characters and the NUL).
+bool rule_parse(const char *text, uint32_t *birth, uint32_t *survive);
+void rule_format(uint32_t birth, uint32_t survive, char out[24]);
+
 // The dataflow queue head is 32-bit: one launch may hold at most
 // kFlowMaxHead pulls (its items plus one extra pull per resident workgroup).
 // flow_chunk_passes: passes of `tiles` items each one launch of `grid`

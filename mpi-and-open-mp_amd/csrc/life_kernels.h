@@ -36,9 +36,12 @@ struct Wrap {
     bool x, y;
 };
 
-// One generation over `reg`: reads `in`, writes `out`.
+// One generation over `reg`: reads `in`, writes `out`.  `rule` (here and in
+// launch_tstep; bit encoding only): the words of a rule other than B3/S23
+// (life::rule_words) -- the launch then runs the table-rule instance of the
+// same kernel; null: B3/S23.
 hipError_t launch_step(const life_layout &L, const uint8_t *in, uint8_t *out, uint8_t *sink,
-                       const Region &reg, Wrap wrap, hipStream_t s);
+                       const Region &reg, Wrap wrap, hipStream_t s, const RuleWords *rule = nullptr);
 
 // Tuning knobs of the stencil (rows per lane, rows of loads in flight);
 // defaults chosen by measurement, overridable by LIFE_STEP_ROWS / LIFE_STEP_DEPTH.
@@ -98,7 +101,8 @@ bool flow_ok(const life_layout &L, int m);
 // banded rows unless work_only)
 int64_t flow_items_per_pass(const life_layout &L, int m, bool work_only = false);
 int flow_slots(const life_layout &L);  // resident workgroups of L's dataflow kernel on this device
-int tile_slots(const life_layout &L);  // resident workgroups of L's per-launch tile kernel on this device
+// resident workgroups of L's per-launch tile kernel on this device (rule: of its table-rule instance)
+int tile_slots(const life_layout &L, bool rule = false);
 // ev0 / ev1 (optional): events stamped with the kernel dispatch's own start
 // and end (hipExtLaunchKernel) -- no event packets between launches.
 // One empty launch of the dataflow instance launch_tflow(L, m, flow) would use
@@ -129,13 +133,13 @@ struct Extend {
 hipError_t launch_tstep(const life_layout &L, const uint8_t *in, uint8_t *out, const TileRegion *r, int nreg,
                         int m, Wrap wrap, hipStream_t s,
                         double *valu_lane_ops = nullptr, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
-                        Extend ext = Extend{}, int64_t concurrent = 0);
+                        Extend ext = Extend{}, int64_t concurrent = 0, const RuleWords *rule = nullptr);
 // Computes (and caches) the launch-tail plans launch_tstep will use for the
 // whole-shard launches of layout L at m = 1 .. mmax generations (with
 // ext_y: also every deep-halo extension 0 .. K - m), so that a step call
 // does not pay the planner's search (~50 us per new shape) before its first
 // launch.
-void prewarm_tail_plans(const life_layout &L, int mmax, bool ext_y);
+void prewarm_tail_plans(const life_layout &L, int mmax, bool ext_y, bool rule = false);
 // The layout a deep-halo pass tiles: h + 2 ext.y rows starting ext.y rows
 // into the top apron.
 life_layout extended_layout(const life_layout &L, const Extend &ext);
@@ -144,7 +148,11 @@ int tile_waves(bool bit);         // waves per tile workgroup: 8
 // VALU instructions the lanes at one lane position of a tile's waves issue
 // for m generations (the op-count model of life_kernels.hip tstep_kernel,
 // checked against the SQ_INSTS_VALU counter in profiles/); x 64 lanes x tiles.
-double tstep_valu_per_tile_lane(int m, bool byte);
+double tstep_valu_per_tile_lane(int m, bool byte, bool rule = false);
+// VALU instructions per pair row and generation of the table-rule tiles
+// (trule_bit_kernel): 2 v_alignbit + 4 (two full adders) + 2 x 25 (the tail);
+// B3/S23: 22.  life_mi355x.RULE_VALU_PER_PAIR_ROW in the binding.
+constexpr int kRuleValuPerPairRow = 56;
 void set_temporal_rows(int kernel, int nr);  // kernel -1: both encodings (values valid for each)
 
 // LDS-resident path for small single-shard grids: all `gens` generations in

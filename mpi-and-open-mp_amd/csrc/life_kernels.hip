@@ -21,6 +21,9 @@
 //    sum per row; three rows add to n9 = u0 + 2*S; alive' = (n9 == 3) |
 //    (alive & n9 == 4).  Every boolean step is one v_bitop3_b32 (per pair:
 //    2 funnel shifts + 4 ops for the two rows sums, 2 x 8 for the rule).
+//    Other Life-like rules (life_dev_set_rule) run table-rule instances of
+//    the same bit kernels: the rule is a compile-time policy on the shared
+//    bodies (ConwayRule / TableRule, life_bitops.h), 2 x 25 for the rule.
 #include "life_kernels.h"
 #include "life_bitops.h"
 #include "life_diag.h"
@@ -155,8 +158,9 @@ __device__ __forceinline__ typename E::H row_sum(const Lane &c, RowData &r) {
 
 // N output rows starting at owned row ys (owned rows ys-1 .. ys+N are read),
 // D rows of loads kept in flight.
-template <class E, int N, int D, bool WRAPX>
-__device__ __forceinline__ void strip_full(const Lane &c, int64_t ys, uint8_t *dst, int64_t spitch) {
+template <class E, int N, int D, bool WRAPX, class RP = ConwayRule>
+__device__ __forceinline__ void strip_full(const Lane &c, int64_t ys, uint8_t *dst, int64_t spitch,
+                                           const RP &rp = RP{}) {
     static_assert(D <= N + 2, "prefetch deeper than the strip");
     RowData q[D];
 #pragma unroll
@@ -174,7 +178,10 @@ __device__ __forceinline__ void strip_full(const Lane &c, int64_t ys, uint8_t *d
             hc = hn;
             cc = r.d;
         } else {
-            *reinterpret_cast<uint4 *>(dst) = E::rule(hp, hc, hn, cc);
+            if constexpr (RP::kTable)
+                *reinterpret_cast<uint4 *>(dst) = rule_unit(rp, hp, hc, hn, cc);
+            else
+                *reinterpret_cast<uint4 *>(dst) = E::rule(hp, hc, hn, cc);
             dst += spitch;
             hp = hc;
             hc = hn;
@@ -183,8 +190,9 @@ __device__ __forceinline__ void strip_full(const Lane &c, int64_t ys, uint8_t *d
     }
 }
 
-template <class E, bool WRAPX>
-__device__ __forceinline__ void strip_tail(const Lane &c, int64_t ys, int n, uint8_t *dst, int64_t spitch) {
+template <class E, bool WRAPX, class RP = ConwayRule>
+__device__ __forceinline__ void strip_tail(const Lane &c, int64_t ys, int n, uint8_t *dst, int64_t spitch,
+                                           const RP &rp = RP{}) {
     RowData r = load_row<WRAPX>(c, ys - 1);
     typename E::H hp = row_sum<E, WRAPX>(c, r);
     r = load_row<WRAPX>(c, ys);
@@ -194,7 +202,10 @@ __device__ __forceinline__ void strip_tail(const Lane &c, int64_t ys, int n, uin
     for (int i = 0; i < n; ++i) {
         r = load_row<WRAPX>(c, ys + 1 + i);
         const typename E::H hn = row_sum<E, WRAPX>(c, r);
-        *reinterpret_cast<uint4 *>(dst) = E::rule(hp, hc, hn, cc);
+        if constexpr (RP::kTable)
+            *reinterpret_cast<uint4 *>(dst) = rule_unit(rp, hp, hc, hn, cc);
+        else
+            *reinterpret_cast<uint4 *>(dst) = E::rule(hp, hc, hn, cc);
         dst += spitch;
         hp = hc;
         hc = hn;
@@ -265,6 +276,87 @@ __global__ __launch_bounds__(kBlock) void step_kernel(StepArgs a) {
         strip_full<E, R, D, WRAPX>(c, ys, dst, spitch);
     else
         strip_tail<E, WRAPX>(c, ys, (int)n, dst, spitch);
+}
+
+// step_kernel's text again, under a rule policy, for the table-rule kernel
+// below.  A twin, not a body both kernels call: with the B3/S23 kernels routed
+// through a shared body (by reference or by value) 18 to 31 of this unit's 133
+// B3/S23 instances compiled to other schedules, a few instructions each, and
+// rules must leave those code objects as they were.  Keep the two in step.
+template <class E, int R, int D, bool WRAPX, class RP>
+__device__ __forceinline__ void step_body(const StepArgs &a, const RP &rp) {
+    int64_t b = blockIdx.x;
+    if (a.xcd) {
+        const int64_t n = (int64_t)gridDim.x, x = b & 7, k = b >> 3, per = n >> 3, rem = n & 7;
+        b = (x < rem ? x * (per + 1) : rem * (per + 1) + (x - rem) * per) + k;
+    }
+    const int64_t bx = b % a.nbx, by = b / a.nbx;
+    const int lane = threadIdx.x & 63;
+    const int64_t wbase = a.u0 + (bx * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * 64;
+    if (wbase >= a.u1) return;  // the whole wave is right of the region
+    const int64_t ys = a.r0 + by * R;
+    const int64_t u = wbase + lane;
+    const int64_t uc = u < a.units ? u : a.units;  // unit `units` is in-pitch: right-neighbour provider
+    Lane c;
+    c.in = a.in;
+    c.pitch = a.pitch;
+    c.h = a.h;
+    c.ya = a.ya;
+    c.wrapy = a.wrapy != 0;
+    c.xoff = a.xoff;
+    c.off = a.xoff + 16 * uc;
+    c.exoff = c.off;
+    c.exshift = 0;
+    if (lane == 0) c.exoff = c.off - 4;
+    if (lane == 63 && u < a.units) c.exoff = c.off + 16;
+    c.needex = lane == 0 || lane == 63;
+    c.pmask = make_uint4(0u, 0u, 0u, 0u);
+    c.pshift = 0;
+    c.pright = false;
+    if (WRAPX) {
+        if (u == 0) {  // left of cell 0 is cell w-1
+            const int64_t wl = a.w - 1;
+            c.exoff = a.xoff + E::dword_of(wl) * 4;
+            c.exshift = E::top_shift(wl);
+            c.needex = true;
+        }
+        if (u == a.units - 1) {  // right of cell w-1 is cell 0
+            const int64_t q = a.w - (a.units - 1) * E::kCellsPerUnit;  // 1 .. kCellsPerUnit
+            if (q == E::kCellsPerUnit) {
+                c.pright = true;
+            } else {
+                const int comp = (int)E::dword_of(q);
+                const uint32_t m = E::kCell0 << E::pos_in_dword(q);
+                c.pshift = E::pos_in_dword(q);
+                c.pmask.x = comp == 0 ? m : 0u;
+                c.pmask.y = comp == 1 ? m : 0u;
+                c.pmask.z = comp == 2 ? m : 0u;
+                c.pmask.w = comp == 3 ? m : 0u;
+            }
+        }
+    }
+    const bool st = u < a.u1;
+    uint8_t *dst = st ? a.out + (ys + a.ya) * a.pitch + a.xoff + 16 * u : a.sink + 16 * lane;
+    const int64_t spitch = st ? a.pitch : 0;
+    const int64_t n = a.r1 - ys < R ? a.r1 - ys : R;
+    if (n == R)
+        strip_full<E, R, D, WRAPX>(c, ys, dst, spitch, rp);
+    else
+        strip_tail<E, WRAPX>(c, ys, (int)n, dst, spitch, rp);
+}
+
+// The one-generation bit kernel under a table rule (life_dev_set_rule): what
+// narrow or short blocks run.  One strip shape (kRuleStepRows rows per lane,
+// 4 rows of loads in flight): these blocks are small, life_tune does not
+// reach it.
+constexpr int kRuleStepRows = 16;
+struct RStepArgs {
+    StepArgs s;
+    RuleWords w;
+};
+template <bool WRAPX>
+__global__ __launch_bounds__(kBlock) void rule_step_kernel(RStepArgs a) {
+    step_body<BitEnc, kRuleStepRows, 4, WRAPX>(a.s, TableRule(a.w));
 }
 
 // ------------------------------------------------------------------ temporal
@@ -382,10 +474,11 @@ struct XchB {
 #define LIFE_FAST_WRAP 1
 #endif
 
-template <int R, bool WRAPX, bool WRAPY, int FLOW, int NW, bool BAND = false>
+template <int R, bool WRAPX, bool WRAPY, int FLOW, int NW, bool BAND = false, class RP = ConwayRule>
 __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in, uint8_t *out, int64_t tx,
                                               int64_t ty, XchB<NW> &xb, int gsh = 6, int nb = 1,
-                                              int64_t ybase = 0, int64_t yend = -1, int64_t org = 0, int own = 62) {
+                                              int64_t ybase = 0, int64_t yend = -1, int64_t org = 0, int own = 62,
+                                              const RP &rule = RP{}) {
     XchP<NW> &xch = xb.s;
     static_assert(R >= 3, "window");
     const int K = a.m;  // ghost rows per window end
@@ -488,8 +581,8 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
             // the wave above (slot 0 above the window: zero, dead ghost rows)
             const uint32_t ae0 = xch[par][wi][4][lane], ae1 = xch[par][wi][5][lane];
             const uint32_t ao0 = xch[par][wi][6][lane], ao1 = xch[par][wi][7][lane];
-            ve[0] = BitEnc::rule1(ae0, ae1, pe0, pe1, ce0, ce1, ve[0]);
-            vo[0] = BitEnc::rule1(ao0, ao1, po0, po1, co0, co1, vo[0]);
+            ve[0] = rule(ae0, ae1, pe0, pe1, ce0, ce1, ve[0]);
+            vo[0] = rule(ao0, ao1, po0, po1, co0, co1, vo[0]);
         }
         constexpr int BAH = FLOW ? LIFE_FLOW_BP_AHEAD : 0;  // permutes ahead (dataflow tiles only)
         uint32_t bl[BAH > 0 ? BAH : 1], br[BAH > 0 ? BAH : 1];
@@ -523,8 +616,8 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
             } else {
                 hsum(ve[r + 1], vo[r + 1], ne0, ne1, no0, no1);
             }
-            ve[r] = BitEnc::rule1(pe0, pe1, ce0, ce1, ne0, ne1, ve[r]);
-            vo[r] = BitEnc::rule1(po0, po1, co0, co1, no0, no1, vo[r]);
+            ve[r] = rule(pe0, pe1, ce0, ce1, ne0, ne1, ve[r]);
+            vo[r] = rule(po0, po1, co0, co1, no0, no1, vo[r]);
             pe0 = ce0;
             pe1 = ce1;
             po0 = co0;
@@ -538,8 +631,8 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
             // the wave below (slot NW + 1 below the window: zero)
             const uint32_t de0 = xch[par][wi + 2][0][lane], de1 = xch[par][wi + 2][1][lane];
             const uint32_t do0 = xch[par][wi + 2][2][lane], do1 = xch[par][wi + 2][3][lane];
-            ve[R - 1] = BitEnc::rule1(pe0, pe1, ce0, ce1, de0, de1, ve[R - 1]);
-            vo[R - 1] = BitEnc::rule1(po0, po1, co0, co1, do0, do1, vo[R - 1]);
+            ve[R - 1] = rule(pe0, pe1, ce0, ce1, de0, de1, ve[R - 1]);
+            vo[R - 1] = rule(po0, po1, co0, co1, do0, do1, vo[R - 1]);
         }
     }
     // window rows [K, NW*R - K) are the tile's owned rows [ty*T, ty*T + T);
@@ -748,9 +841,9 @@ constexpr int bit_wpe(int NW, int R) { return NW == 16 ? (R <= 16 ? 8 : 4) : (R 
 // Banded item i of a region's last tile column: tile rows [ty0, ty0 + rows)
 // as the items of sub-column 0 (ceil(rows / B_0), B_i = 64 >> bgsh[i] tile
 // rows each), then those of sub-column 1.  Wave-uniform throughout.
-template <int RS, bool WRAPX, bool WRAPY, int NW>
+template <int RS, bool WRAPX, bool WRAPY, int NW, class RP = ConwayRule>
 __device__ __forceinline__ void band_item(const TArgs &a, int64_t i, int64_t ty0, int64_t rows, XchB<NW> &xch,
-                                          int64_t ybase = 0, int64_t yend = -1) {
+                                          int64_t ybase = 0, int64_t yend = -1, const RP &rule = RP{}) {
     const int64_t n0 = (rows + (64 >> a.bgsh[0]) - 1) >> (6 - a.bgsh[0]);
     const bool second = a.nband > 1 && i >= n0;
     if (second) i -= n0;
@@ -758,7 +851,8 @@ __device__ __forceinline__ void band_item(const TArgs &a, int64_t i, int64_t ty0
     const int64_t org = second ? a.borg[1] : a.borg[0];
     const int64_t B = 64 >> gsh, t = i * B;  // first tile row of the item within the region
     const int nb = (int)(rows - t < B ? rows - t : B);
-    tile_body_bit<RS, WRAPX, WRAPY, 0, NW, true>(a, a.in, a.out, 0, ty0 + t, xch, gsh, nb, ybase, yend, org, own);
+    tile_body_bit<RS, WRAPX, WRAPY, 0, NW, true>(a, a.in, a.out, 0, ty0 + t, xch, gsh, nb, ybase, yend, org, own,
+                                                 rule);
 }
 
 // Item i of the tail (TArgs::tail_*): RS rows per wave, tile rows of TS =
@@ -768,17 +862,17 @@ __device__ __forceinline__ void band_item(const TArgs &a, int64_t i, int64_t ty0
 // tiles per row without it.  (Round 5's half tiles spanned
 // the last column as full-width tiles; banded they take (64 - o - 2) / 64
 // fewer lanes there.)
-template <int RS, bool WRAPX, bool WRAPY, int NW>
-__device__ __forceinline__ void tail_item(const TArgs &a, int64_t i, XchB<NW> &xch) {
+template <int RS, bool WRAPX, bool WRAPY, int NW, class RP = ConwayRule>
+__device__ __forceinline__ void tail_item(const TArgs &a, int64_t i, XchB<NW> &xch, const RP &rule = RP{}) {
     const int64_t TS = (int64_t)NW * RS - 2 * a.m, y0 = a.tail_y, yend = a.tail_yend;
     const int64_t rows = (yend - y0 + TS - 1) / TS;
     const bool band = a.nband > 0 && a.tail_tx0 + a.tail_ntx == a.btx1;
     const int64_t ntxs = a.tail_ntx - (band ? 1 : 0), nfull = ntxs * rows;
     if (i < nfull)
-        tile_body_bit<RS, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, a.tail_tx0 + i % ntxs, i / ntxs, xch, 6, 1, y0,
-                                              yend);
+        tile_body_bit<RS, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, a.tail_tx0 + i % ntxs, i / ntxs, xch, 6, 1, y0, yend,
+                                              0, 62, rule);
     else
-        band_item<RS, WRAPX, WRAPY, NW>(a, i - nfull, 0, rows, xch, y0, yend);
+        band_item<RS, WRAPX, WRAPY, NW>(a, i - nfull, 0, rows, xch, y0, yend, rule);
 }
 
 // One workgroup per tile (or banded item / partial-height tail tile).
@@ -815,6 +909,61 @@ __global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tstep_bit_kernel(TArg
         band_item<R, WRAPX, WRAPY, NW>(a, wr - nfull, a.ty0[k], a.ty1[k] - a.ty0[k], xch);
     }
     wg_trace(1);
+}
+
+
+// tstep_bit_kernel's item dispatch again, under a rule policy, for the
+// table-rule kernel below (a twin for the reason given at step_body: the
+// B3/S23 instances keep their own text and so their code).
+template <int R, bool WRAPX, bool WRAPY, int NW, class RP>
+__device__ __forceinline__ void tstep_bit_body(const TArgs &a, XchB<NW> &xch, const RP &rule) {
+    wg_trace(0);
+    int64_t wg = blockIdx.x;
+    if (wg < a.xcd_n) {  // per-XCD row-major runs, as tstep_bit_kernel
+        const int64_t n = a.xcd_n, x = wg & 7, k = wg >> 3, per = n >> 3, rem = n & 7;
+        wg = (x < rem ? x * (per + 1) : rem * (per + 1) + (x - rem) * per) + k;
+    }
+    if (a.tail_ntx > 0 && wg >= a.tail_first) {
+        tail_item<R / 2, WRAPX, WRAPY, NW>(a, wg - a.tail_first, xch, rule);
+        wg_trace(1);
+        return;
+    }
+    const int64_t nwg = a.first[a.nreg];
+    if (wg >= nwg) return;  // whole workgroup
+    int k = 0;
+    while (k + 1 < a.nreg && wg >= a.first[k + 1]) ++k;
+    const int64_t wr = wg - a.first[k];
+    const bool bands = a.nband > 0 && a.tx1[k] == a.btx1;
+    const int64_t ntx = a.tx1[k] - a.tx0[k] - (bands ? 1 : 0);
+    const int64_t nfull = ntx * (a.ty1[k] - a.ty0[k]);
+    if (wr < nfull) {
+        const int64_t tx = a.tx0[k] + wr % ntx, ty = a.ty0[k] + wr / ntx;
+        tile_body_bit<R, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, tx, ty, xch, 6, 1, 0, -1, 0, 62, rule);
+    } else {
+        band_item<R, WRAPX, WRAPY, NW>(a, wr - nfull, a.ty0[k], a.ty1[k] - a.ty0[k], xch, 0, -1, rule);
+    }
+    wg_trace(1);
+}
+
+// The same tiles under a table rule (life_dev_set_rule): the tail is 25
+// v_bitop3 per dword instead of 12 and its 20 uniform words live in VGPRs,
+// so the instance is compiled for 2 tiles per CU (4 waves per SIMD, at most
+// 128 VGPRs) rather than squeezed into the 80 of 3 tiles.  VALU per pair row
+// and generation: 2 v_alignbit + 2 full adders (4) + 2 x 25 =
+// kRuleValuPerPairRow (life_kernels.h; pinned against the code object by
+// tests/test_isa_rule.py).
+// (LIFE_RULE_WPE, compile time, A/B: 6 = 3 tiles per CU at <= 80 VGPRs)
+#ifndef LIFE_RULE_WPE
+#define LIFE_RULE_WPE 4
+#endif
+struct RTArgs {
+    TArgs t;
+    RuleWords w;
+};
+template <int R, bool WRAPX, bool WRAPY, int NW>
+__global__ __launch_bounds__(64 * NW, LIFE_RULE_WPE) void trule_bit_kernel(RTArgs a) {
+    __shared__ XchB<NW> xch;
+    tstep_bit_body<R, WRAPX, WRAPY, NW>(a.t, xch, TableRule(a.w));
 }
 
 template <int R, int GK, bool WRAPX, bool WRAPY, int NW>
@@ -1327,9 +1476,10 @@ int tile_waves(bool) { return kStackWaves; }
 // rule for both dwords (16 v_bitop3) = 22 (+ 2 ds_bpermute on the LDS pipe);
 // byte, per word row: the drifting frame (12) plus pack (8 v_dot4 + 3
 // shifts) and unpack (8 x bfe/mul24/and) once per row and launch.
-double tstep_valu_per_tile_lane(int m, bool byte) {
+double tstep_valu_per_tile_lane(int m, bool byte, bool rule) {
     if (byte) return (double)kStackWaves * (double)temporal_rows(false) * (12.0 * (double)m + 35.0);
-    return (double)tile_waves(true) * (double)temporal_rows(true) * 22.0 * (double)m;
+    return (double)tile_waves(true) * (double)temporal_rows(true) * (rule ? (double)kRuleValuPerPairRow : 22.0) *
+           (double)m;
 }
 
 void set_temporal_rows(int kernel, int nr) {
@@ -1387,10 +1537,12 @@ static bool onegen_xcd_enabled(bool bit) {
 }
 
 hipError_t launch_step(const life_layout &L, const uint8_t *in, uint8_t *out, uint8_t *sink,
-                       const Region &reg, Wrap wrap, hipStream_t s) {
+                       const Region &reg, Wrap wrap, hipStream_t s, const RuleWords *rule) {
     if (reg.u1 <= reg.u0 || reg.r1 <= reg.r0) return hipSuccess;
+    if (rule && !is_bit(L)) return hipErrorInvalidValue;  // no quiet B3/S23 in its place
     StepTuning t = step_tuning(is_bit(L));
     if (t.rows != 16 && t.rows != 64) t.rows = 32;
+    if (rule) t.rows = kRuleStepRows;
     StepArgs a;
     a.in = in;
     a.out = out;
@@ -1410,6 +1562,14 @@ hipError_t launch_step(const life_layout &L, const uint8_t *in, uint8_t *out, ui
     a.xcd = onegen_xcd_enabled(is_bit(L)) ? 1 : 0;
     const int64_t nby = (reg.r1 - reg.r0 + t.rows - 1) / t.rows;
     const unsigned grid = (unsigned)(a.nbx * nby);
+    if (rule) {
+        const RStepArgs ra{a, *rule};
+        if (wrap.x)
+            rule_step_kernel<true><<<grid, kBlock, 0, s>>>(ra);
+        else
+            rule_step_kernel<false><<<grid, kBlock, 0, s>>>(ra);
+        return hipGetLastError();
+    }
     return is_bit(L) ? launch_e<BitEnc>(a, t, wrap.x, grid, s) : launch_e<ByteEnc>(a, t, wrap.x, grid, s);
 }
 
@@ -1461,6 +1621,23 @@ const void *bit_k(Wrap wrap) {
     return nullptr;
 }
 const void *tstep_bit_fn() { return bit_k(Wrap{true, true}); }
+
+// the same shapes under a table rule (trule_bit_kernel)
+template <int R, int NW>
+const void *rule_fn(Wrap wrap) {
+    if (wrap.x && wrap.y) return (const void *)trule_bit_kernel<R, true, true, NW>;
+    if (wrap.x) return (const void *)trule_bit_kernel<R, true, false, NW>;
+    if (wrap.y) return (const void *)trule_bit_kernel<R, false, true, NW>;
+    return (const void *)trule_bit_kernel<R, false, false, NW>;
+}
+const void *rule_k(Wrap wrap) {
+    const int R = temporal_rows(true), NW = tile_waves(true);
+#define LIFE_BIT_CASE(r, nw) \
+    if (R == r && NW == nw) return rule_fn<r, nw>(wrap);
+    LIFE_BIT_SHAPES(LIFE_BIT_CASE)
+#undef LIFE_BIT_CASE
+    return nullptr;
+}
 }  // namespace
 
 // Byte tiles are compiled for a fixed ghost depth (a runtime depth measured
@@ -1547,9 +1724,19 @@ static int tstep_bit_slots() {
     }
     return cached;
 }
+// the table-rule tiles of the current shape: 2 per CU, not 3
+static int trule_bit_slots() {
+    static int cached = 0, key = -1;
+    const int k = temporal_rows(true) * 64 + tile_waves(true);
+    if (k != key) {
+        cached = slots_of(rule_k(Wrap{true, true}), 64 * tile_waves(true));
+        key = k;
+    }
+    return cached;
+}
 
-int tile_slots(const life_layout &L) {
-    if (is_bit(L)) return tstep_bit_slots();
+int tile_slots(const life_layout &L, bool rule) {
+    if (is_bit(L)) return rule ? trule_bit_slots() : tstep_bit_slots();
     static int cached = 0, key = -1;
     const int k = temporal_rows(false);
     if (k != key) {
@@ -1584,15 +1771,15 @@ life_layout extended_layout(const life_layout &L, const Extend &ext) {
 // ty1) of tile_geom(L, m), beside `pre` items of another launch dispatched
 // just before it (launch_tstep; cached by life::tail_plan).
 static TailPlan tail_plan_for(const life_layout &L, const TileGeom &g, int m, int64_t tx0, int64_t tx1, int64_t ty0,
-                              int64_t ty1, int64_t pre) {
+                              int64_t ty1, int64_t pre, bool rule) {
     const int64_t T2 = (int64_t)tile_waves(true) * (temporal_rows(true) / 2) - 2 * (int64_t)tile_ghost(L, m);
     const int64_t yend = std::min(ty1 * g.rows, L.h);
     const BandRows b = region_bands(g, tx1);
-    return tail_plan(tx1 - tx0 - (b.n > 0 ? 1 : 0), b, ty0, ty1, yend, g.rows, T2, tstep_bit_slots(),
-                     tail_split_mode(), kTailC, pre);
+    return tail_plan(tx1 - tx0 - (b.n > 0 ? 1 : 0), b, ty0, ty1, yend, g.rows, T2,
+                     rule ? trule_bit_slots() : tstep_bit_slots(), tail_split_mode(), kTailC, pre);
 }
 
-void prewarm_tail_plans(const life_layout &L, int mmax, bool ext_y) {
+void prewarm_tail_plans(const life_layout &L, int mmax, bool ext_y, bool rule) {
     if (!is_bit(L) || L.generations_per_exchange < 2 || tail_split_mode() == 0) return;
     const int K = L.generations_per_exchange;
     for (int m = 1; m <= std::min(mmax, K); ++m)
@@ -1601,7 +1788,7 @@ void prewarm_tail_plans(const life_layout &L, int mmax, bool ext_y) {
             x.y = e;
             const life_layout V = extended_layout(L, x);
             const TileGeom g = tile_geom(V, m);
-            if (g.rows >= 1) (void)tail_plan_for(V, g, m, 0, g.ntx, 0, g.nty, 0);
+            if (g.rows >= 1) (void)tail_plan_for(V, g, m, 0, g.ntx, 0, g.nty, 0, rule);
         }
 }
 
@@ -1619,9 +1806,10 @@ static void set_bands(TArgs &a, const TileGeom &g) {
 
 hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out, const TileRegion *r, int nreg,
                         int m, Wrap wrap, hipStream_t s, double *valu_lane_ops, hipEvent_t ev0, hipEvent_t ev1,
-                        Extend ext, int64_t concurrent) {
+                        Extend ext, int64_t concurrent, const RuleWords *rule) {
     const int K = Lin.generations_per_exchange;
     const bool bit = is_bit(Lin);
+    if (rule && !bit) return hipErrorInvalidValue;  // no quiet B3/S23 in its place
     // m <= 32: the tile's edge lanes absorb at most 32 wrong cells; m <= the
     // apron depth a partitioned axis provides.  Deep-halo passes: bit only
     // (the byte windows hold K ghost rows whatever m is), the window's top
@@ -1673,7 +1861,7 @@ hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out,
         const int64_t tx0 = a.tx0[0], tx1 = a.tx1[0], ty0 = a.ty0[0], ty1 = a.ty1[0];
         const int64_t yend = std::min(ty1 * g.rows, L.h);
         const BandRows bands = region_bands(g, tx1);
-        const TailPlan p = tail_plan_for(L, g, m, tx0, tx1, ty0, ty1, concurrent);
+        const TailPlan p = tail_plan_for(L, g, m, tx0, tx1, ty0, ty1, concurrent, rule != nullptr);
         if (p.F < ty1 && p.F >= ty0) {
             a.ty1[0] = p.F;
             a.first[1] = region_items(g, TileRegion{tx0, tx1, ty0, p.F});
@@ -1688,10 +1876,16 @@ hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out,
     const bool split = a.tail_ntx > 0;
     a.xcd_n = (bit ? xcd_order_enabled() : xcd_order_byte_enabled()) ? (split ? a.tail_first : items) : 0;
     if (valu_lane_ops) {
-        const double lane = 64.0 * tstep_valu_per_tile_lane(m, !bit);
+        const double lane = 64.0 * tstep_valu_per_tile_lane(m, !bit, rule != nullptr);
         *valu_lane_ops = (double)(split ? a.tail_first : items) * lane;
         if (split)  // half tiles: R / 2 register rows per wave
             *valu_lane_ops += (double)(items - a.tail_first) * lane * 0.5;
+    }
+    if (rule) {
+        const void *rfn = rule_k(wrap);
+        if (!rfn) return hipErrorInvalidValue;
+        RTArgs ra{a, *rule};
+        return launch_fn(rfn, (unsigned)items, 64u * (unsigned)tile_waves(true), &ra, s, ev0, ev1);
     }
     const void *fn = bit                      ? bit_k(wrap)
                      : byte_one_ghost(L, m) ? byte_fn<48, 1>(wrap)

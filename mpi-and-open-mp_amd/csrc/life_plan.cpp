@@ -373,6 +373,97 @@ const char *life_dev_strerror(int err) { return life_strerror(err); }
 
 }  // extern "C"
 
+// ---- Life-like rules (life_host.h)
+life::RuleWords life::rule_words(uint32_t birth, uint32_t survive) {
+    RuleWords w;
+    for (int alive = 0; alive < 2; alive++) {
+        auto t = [&](int n9) -> uint32_t {  // next state of a cell whose 3 x 3 block holds n9 live cells
+            const int n8 = n9 - alive;
+            if (n8 < 0 || n8 > 8) return 0u;  // cannot occur
+            return (((alive ? survive : birth) >> n8) & 1u) ? 0xFFFFFFFFu : 0u;
+        };
+        for (int s = 0; s < 5; s++) {
+            w.b[alive][s] = t(2 * s);
+            w.a[alive][s] = t(2 * s) ^ t(2 * s + 1);
+        }
+    }
+    return w;
+}
+
+namespace {
+// digits 0-8 up to `end` (a '/' or the NUL) into a mask
+bool rule_digits(const char *&p, char end, uint32_t *mask) {
+    *mask = 0;
+    for (; *p != end; ++p) {
+        if (*p < '0' || *p > '8') return false;
+        *mask |= 1u << (*p - '0');
+    }
+    return true;
+}
+}  // namespace
+
+bool life::rule_parse(const char *text, uint32_t *birth, uint32_t *survive) {
+    if (!text || !*text) return false;
+    const char *p = text;
+    uint32_t b = 0, s = 0;
+    if (*p == 'B' || *p == 'b') {  // B.../S...
+        ++p;
+        if (!rule_digits(p, '/', &b)) return false;
+        ++p;
+        if (*p != 'S' && *p != 's') return false;
+        ++p;
+        if (!rule_digits(p, '\0', &s)) return false;
+    } else {  // S/B
+        if (!rule_digits(p, '/', &s)) return false;
+        ++p;
+        if (!rule_digits(p, '\0', &b)) return false;
+    }
+    *birth = b;
+    *survive = s;
+    return true;
+}
+
+void life::rule_format(uint32_t birth, uint32_t survive, char out[24]) {
+    char *p = out;
+    *p++ = 'B';
+    for (int k = 0; k <= 8; k++)
+        if ((birth >> k) & 1u) *p++ = (char)('0' + k);
+    *p++ = '/';
+    *p++ = 'S';
+    for (int k = 0; k <= 8; k++)
+        if ((survive >> k) & 1u) *p++ = (char)('0' + k);
+    *p = '\0';
+}
+
+// life_last_error's setter lives with the device runtime (life_dev.hip); a
+// program that links this unit alone (the CPU harnesses) has none
+namespace life {
+namespace rt {
+__attribute__((weak, visibility("hidden"))) void set_err(const char *fmt, ...);
+}
+}  // namespace life
+
+extern "C" {
+
+int life_rule_parse(const char *text, uint32_t *birth, uint32_t *survive) {
+    if (birth && survive && life::rule_parse(text, birth, survive)) return LIFE_OK;
+    if (life::rt::set_err)
+        life::rt::set_err("rule \"%.64s\": expected B<digits>/S<digits> or <digits>/<digits> (S/B), digits 0-8",
+                          text ? text : "(null)");
+    return LIFE_EINVAL;
+}
+
+int life_rule_format(uint32_t birth, uint32_t survive, char out[24]) {
+    if (!out || ((birth | survive) & ~life::kRuleMask)) {
+        if (life::rt::set_err) life::rt::set_err("rule masks 0x%x / 0x%x: bits above 8", birth, survive);
+        return LIFE_EINVAL;
+    }
+    life::rule_format(birth, survive, out);
+    return LIFE_OK;
+}
+
+}  // extern "C"
+
 namespace {
 // Slots grouped by the time they fall free (a list schedule of a few item
 // kinds keeps a handful of distinct free times).

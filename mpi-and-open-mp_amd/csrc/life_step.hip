@@ -28,7 +28,7 @@ namespace {
 int launch_region(life_dev *d, Shard &s, const life::Region &r, bool timed, hipStream_t st) {
     Bracket b;
     CHK(bracket_begin(d, s, timed, 1, kExtNever, false, st, &b));
-    HIPCHK(life::launch_step(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], s.sink, r, wrap_of(d), st));
+    HIPCHK(life::launch_step(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], s.sink, r, wrap_of(d), st, rule_of(d)));
     CHK(bracket_end(b, st));
     if (b.t) {  // (no timer counts it -- span-only timing, LIFE_TIMING_MODE=3: no booking)
         const bool bit = s.lay.kernel == LIFE_KERNEL_BIT;
@@ -50,7 +50,7 @@ int launch_tiles(life_dev *d, Shard &s, const life::TileRegion *r, int nreg, int
     CHK(bracket_begin(d, s, timed, 1, kExtModeExt | kExtModeCall, false, st, &b));
     double valu = 0.0;
     HIPCHK(life::launch_tstep(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], r, nreg, m, wrap_of(d), st, &valu, b.ext_a,
-                              b.ext_b, xt, concurrent));
+                              b.ext_b, xt, concurrent, rule_of(d)));
     CHK(bracket_end(b, st));
     if (b.t) {  // (no timer counts it -- span-only timing, LIFE_TIMING_MODE=3: no booking)
         const life::TileGeom g = life::tile_geom(life::extended_layout(s.lay, xt), m);
@@ -146,7 +146,7 @@ int pipelined_pass(life_dev *d, Shard &s, int m) {
         const life::TileRegion reg{0, g.ntx, P.ty[r], P.ty[r + 1]};
         double v = 0.0;
         HIPCHK(life::launch_tstep(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], &reg, 1, m, wrap_of(d), q, &v, nullptr,
-                                  nullptr, life::Extend{}, -1));
+                                  nullptr, life::Extend{}, -1, rule_of(d)));
         valu += v;
         if (P.record[j]) HIPCHK(hipEventRecord(s.ev_pipe[i % kPipeRing], q));
     }
@@ -355,7 +355,7 @@ int generation_block(life_dev *d, const life::PassPlan &p) {
             int64_t ring_items = 0;
             for (int k = 0; k < n; k++) ring_items += life::region_items(g, ring[k]);
             const int64_t items = life::region_items(g, inner) + ring_items;
-            *halo_side = carry_on_halo_side(items, life::tile_slots(s.lay)) ? 1 : 0;
+            *halo_side = carry_on_halo_side(items, life::tile_slots(s.lay, d->table)) ? 1 : 0;
             // LIFE_INTERIOR_TAIL=1: the interior's launch-tail plan counts the
             // ring's tiles, dispatched just before it, as holding their slots
             // (16384 x 32768's 584 interior tiles beside 249 ring tiles are one
@@ -422,7 +422,8 @@ life::RegWinPlan win_plan(const life_dev *d) {
 }
 
 bool small_grid(const life_dev *d) {
-    if (d->world != 1 || d->shards.size() != 1 || d->small_mode == 0 || d->loop != 0) return false;
+    // (the resident kernels are B3/S23 only: under another rule the streaming kernels run)
+    if (d->world != 1 || d->shards.size() != 1 || d->small_mode == 0 || d->loop != 0 || d->table) return false;
     const life_layout &L = d->shards[0].lay;
     if (win_plan(d).blocks > 0) return true;
     return (d->small_mode != 2 && life::reg_small_rows(L) > 0) ||
@@ -466,9 +467,10 @@ int step_small(life_dev *d, int64_t generations) {
 }
 
 // The dataflow form a single-shard bit device runs its passes of m
-// generations in (1 / 2, the hand-off forms), or 0 (per-launch tiles).
+// generations in (1 / 2, the hand-off forms), or 0 (per-launch tiles; always
+// under a rule other than B3/S23: the dataflow tiles have no such instance).
 int flow_form(const life_dev *d, int *m_out) {
-    if (!d->flow || d->shards.size() != 1 || d->world != 1 || part(d, 0) || part(d, 1) || self_wrap_x(d) ||
+    if (!d->flow || d->table || d->shards.size() != 1 || d->world != 1 || part(d, 0) || part(d, 1) || self_wrap_x(d) ||
         d->kernel != LIFE_KERNEL_BIT)
         return 0;
     const life_layout &L = d->shards[0].lay;
@@ -631,7 +633,7 @@ int pipe_regions(const life_dev *d, int64_t generations) {
     int R = d->pipe;
     if (R == 1) {
         R = kPipeAutoRegions;
-        const int slots = life::tile_slots(L);
+        const int slots = life::tile_slots(L, d->table);
         if (passes < kPipeAutoPasses || slots < 1 ||
             (double)life::region_items(g, life::TileRegion{0, g.ntx, 0, g.nty}) < kPipeAutoRounds * R * slots)
             return 0;

@@ -38,6 +38,9 @@
  *                     first cell at (X, Y) (any integers, wrapped) into an
  *                     empty universe of --nx x --ny cells (both required;
  *                     life_dev_clear + life_dev_set_rect); the dump must fit
+ *   --rule TEXT       the Life-like rule, "B36/S23" or Golly's "23/36" (S/B)
+ *                     (life_rule_parse, life_dev_set_rule; default B3/S23, the
+ *                     reference's rule; bit kernel only, no B0 rules)
  *   --live            print the live-cell count after the run to stderr
  *   --rank-mode       one-process-per-GPU mode even without a launcher (world 1)
  *
@@ -349,6 +352,8 @@ int main(int argc, char **argv) {
     long long o_nx = -1, o_ny = -1, o_steps = -1, o_save = -1;
     unsigned long long seed = 0;
     double density = 0.5;
+    uint32_t birth = LIFE_RULE_CONWAY_BIRTH, survive = LIFE_RULE_CONWAY_SURVIVE; /* --rule */
+    int have_rule = 0;
     for (int a = 1; a < argc; a++) {
         const char *s = argv[a];
         const int more = a + 1 < argc;
@@ -405,6 +410,13 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "life_mi355x: --at takes X,Y (two integers)\n");
                 return 1;
             }
+        }
+        else if (!strcmp(s, "--rule") && more) {
+            if (life_rule_parse(argv[++a], &birth, &survive) != LIFE_OK) {
+                fprintf(stderr, "life_mi355x: --rule: %s\n", life_last_error());
+                return 1;
+            }
+            have_rule = 1;
         }
         else if (!strcmp(s, "--live")) live = 1;
         else if (!strcmp(s, "--rank-mode")) force_rank = 1;
@@ -507,6 +519,7 @@ int main(int argc, char **argv) {
         rc = life_dev_create_ex(c.nx, c.ny, gpus, dims[0], dims[1], kernel, LIFE_XPORT_AUTO, &d);
     }
     if (rc) die("create", rc);
+    if (have_rule && (rc = life_dev_set_rule(d, birth, survive)) != LIFE_OK) die("--rule", rc);
     const int writer = !rank_mode || rank == root; /* the process that writes frames and prints */
     uint8_t *grid = NULL; /* packed rows: bits frames */
     char *body = NULL;    /* VTK cell text */

@@ -52,6 +52,12 @@ BLOCK_GENS = {"bit": 12, "byte": 32}  # tiles: default generations per launch at
 TEMPORAL_ROWS = {"bit": 24, "byte": 48}  # default register rows per wave (bit: 64-cell pair rows)
 TILE_WAVES = {"bit": 8, "byte": 8}  # waves per tile workgroup (window = waves x rows)
 TEMPORAL_XAPRON = {"bit": 64, "byte": 32}  # x-apron of the temporal layouts: one lane column
+# VALU instructions per pair row and generation of the bit tiles under a rule other than B3/S23 (the table
+# tail: 2 v_alignbit + 2 full adders + 2 x 25 v_bitop3; csrc/life_kernels.h kRuleValuPerPairRow) and under
+# B3/S23; life_dev_kernel_work books them, tests/test_isa_rule.py and tests/test_isa.py pin them
+RULE_VALU_PER_PAIR_ROW = 56
+CONWAY_VALU_PER_PAIR_ROW = 22
+RULE_CONWAY = (1 << 3, (1 << 2) | (1 << 3))  # (birth, survive) masks of B3/S23
 
 # Every symbol include/life_mi355x.h declares (checked by tests/test_abi.py).
 ABI_SYMBOLS = (
@@ -66,6 +72,7 @@ ABI_SYMBOLS = (
     "life_dev_strerror", "life_dev_shard_info",
     "life_dev_clear", "life_dev_set_cells", "life_dev_gather_rect", "life_dev_gather_density",
     "life_dev_upload_bits", "life_dev_set_rect",
+    "life_rule_parse", "life_rule_format", "life_dev_set_rule", "life_dev_get_rule",
 )
 PATHS = {0: "none", 1: "onegen", 2: "tiles", 3: "flow", 5: "small"}
 
@@ -170,6 +177,12 @@ def _lib():
             L.life_dev_call_stats.argtypes = [vp, P(ctypes.c_double), P(ctypes.c_double), P(i64), P(ctypes.c_double)]
         if hasattr(L, "life_dev_shard_info"):  # absent from pre-round-6 builds (LIFE_MI355X_LIB A/B runs)
             L.life_dev_shard_info.argtypes = [vp, i32, P(ctypes.c_int), ctypes.c_char_p, P(ctypes.c_int)]
+        if hasattr(L, "life_dev_set_rule"):  # absent from builds that predate rules (LIFE_MI355X_LIB A/B runs)
+            u32 = ctypes.c_uint32
+            L.life_rule_parse.argtypes = [ctypes.c_char_p, P(u32), P(u32)]
+            L.life_rule_format.argtypes = [u32, u32, ctypes.c_char_p]
+            L.life_dev_set_rule.argtypes = [vp, u32, u32]
+            L.life_dev_get_rule.argtypes = [vp, P(u32), P(u32)]
         L.life_tune.argtypes = [i32, i32, i32]
         L.life_tune_temporal.argtypes = [i32, i32]
         L.life_measure_copy.argtypes = [i32, i64, i32, P(ctypes.c_double)]
@@ -245,6 +258,32 @@ def layout_query(nx: int, ny: int, dims, rank: int, kernel="byte") -> Layout:
     return L
 
 
+def parse_rule(text: str):
+    """(birth, survive) masks of a rulestring (life_rule_parse): "B36/S23" in
+    either letter case, or Golly's "23/3" (S/B).  Bit k of birth: a dead cell
+    with k live neighbours is born; of survive: a live one stays alive."""
+    b, s = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(_lib().life_rule_parse(str(text).encode(), ctypes.byref(b), ctypes.byref(s)), "life_rule_parse")
+    return b.value, s.value
+
+
+def format_rule(birth: int, survive: int) -> str:
+    """The canonical "B.../S..." of two 9-bit masks (life_rule_format)."""
+    if not (0 <= int(birth) < 2**32 and 0 <= int(survive) < 2**32):
+        raise ValueError(f"rule masks {birth}, {survive} are not 32-bit")
+    out = ctypes.create_string_buffer(24)
+    _check(_lib().life_rule_format(int(birth), int(survive), out), "life_rule_format")
+    return out.value.decode()
+
+
+def _rule_masks(rule):
+    """A rulestring or a (birth, survive) pair -> the pair."""
+    if isinstance(rule, str):
+        return parse_rule(rule)
+    birth, survive = rule
+    return int(birth), int(survive)
+
+
 def density_to_thr(density: float) -> int:
     return min(int(density * 2.0**32), 0xFFFFFFFF)
 
@@ -286,7 +325,7 @@ class Life:
 
     def __init__(self, nx: int, ny: int, shards: int = 1, kernel="bit", dims=(0, 0),
                  transport: int = XPORT_AUTO, small_grid: bool = True, overlap: bool = True, flow=None,
-                 window=None, _handle=None):
+                 window=None, rule=None, _handle=None):
         self.nx, self.ny = int(nx), int(ny)
         self.kernel = kernel_id(kernel)
         self._h = ctypes.c_void_p()
@@ -313,9 +352,31 @@ class Life:
         # launch per pass)
         if flow is not None:
             self.configure(OPT_FLOW, int(flow))
+        # rule: None (B3/S23), a rulestring or a (birth, survive) pair (set_rule)
+        if rule is not None:
+            self.set_rule(rule)
 
     def configure(self, option: int, value: int) -> None:
         _check(_lib().life_dev_configure(self._h, option, value), "configure")
+
+    def set_rule(self, rule) -> None:
+        """life_dev_set_rule: the Life-like rule of the following steps, a
+        rulestring ("B36/S23", "23/36") or a (birth, survive) pair of 9-bit
+        masks.  Bit encoding only (the byte encoding runs B3/S23), no B0
+        rules; the state is untouched.  Under a rule other than B3/S23 the
+        per-launch tiles and the one-generation kernel run (no dataflow or
+        small-grid kernels)."""
+        birth, survive = _rule_masks(rule)
+        if not (0 <= birth < 2**32 and 0 <= survive < 2**32):
+            raise ValueError(f"rule masks {birth}, {survive} are not 32-bit")
+        _check(_lib().life_dev_set_rule(self._h, birth, survive), "set_rule")
+
+    @property
+    def rule(self) -> str:
+        """The current rule's canonical string (life_dev_get_rule)."""
+        b, s = ctypes.c_uint32(), ctypes.c_uint32()
+        _check(_lib().life_dev_get_rule(self._h, ctypes.byref(b), ctypes.byref(s)), "get_rule")
+        return format_rule(b.value, s.value)
 
     @classmethod
     def for_rank(cls, nx, ny, rank, world, uid: bytes, device: int, kernel="bit", dims=(0, 0)):
