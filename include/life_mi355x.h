@@ -412,7 +412,50 @@ int life_dev_set_timing(life_dev *d, int on);
  * (life_dev_set_timing with LIFE_TIMING_MODE 1 / 2) run as one launch each.
  * Same results; the statistics count one launch per pass either way. */
 #define LIFE_OPT_PIPELINE 11
+/* LIFE_OPT_SKIP_DEAD (default 0; 1 on; any other value LIFE_EINVAL): step a
+ * sparse universe in the time of its live area.  While on, a step call runs
+ * every pass as a skip-dead pass on a device that qualifies: a single shard in
+ * a single process, both axes wrapped by the stencil (no partitioned axis, no
+ * LIFE_OPT_LOOPBACK, a width that is a multiple of 64), the bit encoding, a
+ * temporal layout, and a grid that does not take the small-grid path.  Such a
+ * pass runs only the tiles whose input window -- the owned rows plus m ghost
+ * rows at each end, the owned pair columns plus one edge lane column at each
+ * side, wrapped periodically -- may hold a live cell; every other tile's
+ * owned block ends up all dead in the destination buffer without the tile
+ * body running ("nothing is born from nothing": B0 rules are refused by
+ * life_dev_set_rule).  Results are bit-identical to the ordinary tiles, under
+ * B3/S23 and under every rule life_dev_set_rule accepts.  The option decides
+ * after LIFE_OPT_SMALL_GRID and before LIFE_OPT_FLOW / LIFE_OPT_PIPELINE: such
+ * a call runs neither the dataflow form nor pipelined regions, and
+ * life_dev_last_path returns LIFE_PATH_SKIP.  On every other device (byte
+ * encoding, more than one shard, rank mode with world > 1, a width that is
+ * no multiple of 64, a small grid) the option is accepted and has no effect,
+ * as LIFE_OPT_FLOW.  The call stays asynchronous: nothing per pass is read
+ * back, nothing is waited for.
+ * What a tile may skip is kept in one activity map per grid buffer (per tile
+ * column x 32 rows, row masks "this row of the block may hold a live cell":
+ * in any pair, in its first pair, in its last pair), which the skip-dead
+ * passes maintain themselves.  Every other writer of the state
+ * invalidates the maps: life_dev_upload, life_dev_upload_bits,
+ * life_dev_fill_random, life_dev_clear, life_dev_set_cells, life_dev_set_rect,
+ * a step pass of any other form (the option toggled, a small-grid call), and
+ * turning the option on; life_dev_set_rule leaves them valid.  The next step
+ * call then rebuilds them first with one streaming scan of the grid (about
+ * the cost of life_dev_live_count).
+ * Timing (life_dev_set_timing): a skip-dead pass is ONE timed launch (its
+ * plan kernel, map clear and tile launch under one bracket);
+ * life_dev_kernel_work books the whole grid's cell-updates for it, while
+ * bytes_per_launch and the VALU count are booked as 0 -- the host does not
+ * know how many tiles ran without a readback; life_dev_activity does. */
+#define LIFE_OPT_SKIP_DEAD 12
 int life_dev_configure(life_dev *d, int option, int value);
+/* The skip-dead passes of the LAST life_dev_step call, summed: their number,
+ * the tiles whose body ran, the tiles that only stored zeros over a block the
+ * destination buffer held as possibly live, and the tiles of their tile
+ * grids (run + cleared + skipped).  Blocking: waits for the device and reads
+ * the counters.  Zeros when the last call ran no such pass.  Any out pointer
+ * may be NULL. */
+int life_dev_activity(life_dev *d, int64_t *passes, int64_t *tiles_run, int64_t *tiles_cleared, int64_t *tiles_total);
 /* The rule the device evolves under (masks as life_rule_parse gives them); a
  * new device runs B3/S23.  life_dev_set_rule waits for queued work, as
  * life_dev_configure does, and may be called between any two step calls; the
@@ -439,12 +482,14 @@ int life_dev_get_rule(life_dev *d, uint32_t *birth, uint32_t *survive);
 /* The kernel family that ran the bulk of the last life_dev_step call:
  * LIFE_PATH_ONEGEN (one generation per launch), _TILES (temporally blocked
  * tiles, one launch per pass), _FLOW (the dataflow tiles, LIFE_OPT_FLOW),
- * _SMALL (a small-grid resident kernel); _NONE before the first step. */
+ * _SMALL (a small-grid resident kernel), _SKIP (skip-dead passes,
+ * LIFE_OPT_SKIP_DEAD); _NONE before the first step. */
 #define LIFE_PATH_NONE 0
 #define LIFE_PATH_ONEGEN 1
 #define LIFE_PATH_TILES 2
 #define LIFE_PATH_FLOW 3
 #define LIFE_PATH_SMALL 5
+#define LIFE_PATH_SKIP 6
 int life_dev_last_path(life_dev *d);
 int life_dev_kernel_stats(life_dev *d, double *avg_ms, int64_t *launches, double *bytes_per_launch);
 /* The same timed launches: mean cell-updates per launch (cells x generations

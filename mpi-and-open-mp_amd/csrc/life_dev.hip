@@ -137,6 +137,9 @@ void shard_free(Shard &s) {
     for (uint8_t *p : {s.buf[0], s.buf[1], s.col_send, s.col_recv, s.sink, s.stage})
         if (p) (void)hipFree(p);
     if (s.flow) (void)hipFree(s.flow);
+    if (s.act_map[0]) (void)hipFree(s.act_map[0]);  // one allocation holds both maps
+    if (s.act_cls) (void)hipFree(s.act_cls);
+    if (s.act_cnt) (void)hipFree(s.act_cnt);
     if (s.d_count) (void)hipFree(s.d_count);
     if (s.h_count) (void)hipHostFree(s.h_count);
     for (hipEvent_t e : {s.ev_halo, s.ev_sync, s.ev_int, s.ev_entry, s.own_a, s.own_b})
@@ -537,6 +540,12 @@ int life_dev_configure(life_dev *d, int option, int value) {
     case LIFE_OPT_FLOW_CHUNK:
         if (value < 0) return LIFE_EINVAL;
         d->flow_chunk = value;
+        return LIFE_OK;
+    case LIFE_OPT_SKIP_DEAD:
+        // accepted on every device; it acts where life_step.hip skip_dead_applies
+        if (value < 0 || value > 1) return LIFE_EINVAL;
+        if (value) d->act_valid = false;  // turning it on: the maps are rebuilt by the next step call
+        d->skip_dead = value != 0;
         return LIFE_OK;
     case LIFE_OPT_LOOPBACK: {
         // 1: both axes, 2: x only, 3: y only (the axes a real partition of

@@ -98,6 +98,13 @@ struct Shard {
     unsigned int *flow = nullptr;  // dataflow tiles: queue head, error word, per-tile pass counts (grows on demand)
     size_t flow_words = 0;
     bool flow_used = false;  // a dataflow launch since the last sync checked its error word
+    // skip-dead passes (LIFE_OPT_SKIP_DEAD; allocated by the first such call): act_map[i] is buf[i]'s
+    // activity map (life_act.h), act_cls the tiles' classes of the current pass (grows on demand),
+    // act_cnt the call's counters: tiles run, cleared, skipped
+    uint32_t *act_map[2] = {nullptr, nullptr};
+    uint8_t *act_cls = nullptr;
+    size_t act_cls_cap = 0;
+    unsigned long long *act_cnt = nullptr;
     std::vector<life_halo_op> plan;
     bool corners = false;  // the plan exchanges the four corner blocks itself (fused, one phase)
     // resolved with the plan (plan_halos): every op's staging slot; LOCAL
@@ -149,6 +156,11 @@ struct life_dev {
         int64_t pass = 0;
         life::PipePlan plan;
     } pipe_call;
+    // LIFE_OPT_SKIP_DEAD: the option; whether both activity maps describe their buffers (dropped by every
+    // writer of the state that is not a skip-dead pass, life_act.h); the skip-dead passes of the last
+    // step call and the tiles of their grids (life_dev_activity)
+    bool skip_dead = false, act_valid = false;
+    int64_t act_passes = 0, act_total = 0;
     life::rt::TimedLaunch *call_timer = nullptr;  // kTimeCall: the pair bracketing the current step call
     std::vector<life::rt::Shard> shards;
     double acc_ms = 0.0;

@@ -10,6 +10,7 @@ extern "C" {
 
 int life_dev_upload(life_dev *d, const uint8_t *grid) {
     if (!d || !grid) return LIFE_EINVAL;
+    d->act_valid = false;  // every writer of the state drops the activity maps (LIFE_OPT_SKIP_DEAD)
     for (Shard &s : d->shards) {
         const life_layout &L = s.lay;
         HIPCHK(hipSetDevice(s.device));
@@ -32,6 +33,7 @@ int life_dev_upload(life_dev *d, const uint8_t *grid) {
 
 int life_dev_fill_random(life_dev *d, uint64_t seed, uint32_t thr32) {
     if (!d) return LIFE_EINVAL;
+    d->act_valid = false;
     uint64_t z = seed + 0x9E3779B97F4A7C15ull;  // key = splitmix64(seed)
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
@@ -240,6 +242,7 @@ int life_dev_checksum(life_dev *d, uint64_t *sum) {
 int life_dev_clear(life_dev *d) {
     if (!d) return LIFE_EINVAL;
     CHK(life_dev_sync(d));  // behind the work on all three streams
+    d->act_valid = false;
     for (Shard &s : d->shards) {
         HIPCHK(hipSetDevice(s.device));
         HIPCHK(hipMemsetAsync(s.buf[s.cur], 0, (size_t)(s.lay.pitch * s.lay.rows), s.stream));
@@ -251,6 +254,7 @@ int life_dev_clear(life_dev *d) {
 int life_dev_set_cells(life_dev *d, const int64_t *xy, int64_t n, int alive) {
     if (!d || n < 0 || (n > 0 && !xy)) return LIFE_EINVAL;
     if (n == 0) return LIFE_OK;
+    d->act_valid = false;
     CHK(life_dev_sync(d));  // the edit orders behind the work on all three streams
     constexpr int64_t kChunk = 1 << 20;  // pairs staged at a time (16 MiB)
     for (int64_t i = 0; i < n; i += kChunk) {
@@ -279,6 +283,7 @@ int life_dev_set_cells(life_dev *d, const int64_t *xy, int64_t n, int alive) {
 
 int life_dev_upload_bits(life_dev *d, const uint8_t *packed) {
     if (!d || !packed) return LIFE_EINVAL;
+    d->act_valid = false;
     CHK(life_dev_sync(d));  // as life_dev_set_cells
     const int64_t frb = (d->nx + 7) / 8;  // the frame's row bytes (64-bit offsets: 4 GiB at 2^35 cells)
     for (Shard &s : d->shards) {
@@ -373,6 +378,7 @@ int life_dev_gather_rect(life_dev *d, int64_t x0, int64_t y0, int64_t w, int64_t
 
 int life_dev_set_rect(life_dev *d, int64_t x0, int64_t y0, int64_t w, int64_t h, const uint8_t *cells) {
     if (!d || !cells || w < 1 || h < 1 || w > d->nx || h > d->ny) return LIFE_EINVAL;
+    d->act_valid = false;
     CHK(life_dev_sync(d));  // the edit orders behind the work on all three streams
     const int64_t ax = floor_mod(x0, d->nx), ay = floor_mod(y0, d->ny);
     for (Shard &s : d->shards) {

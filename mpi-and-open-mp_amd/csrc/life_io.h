@@ -92,6 +92,11 @@ hipError_t launch_paste_piece(const life_layout &L, uint8_t *buf, int64_t lx0, i
 hipError_t launch_density(const life_layout &L, const uint8_t *buf, int64_t fx, int64_t fy, int64_t bw,
                           uint32_t *map, hipStream_t s);
 
+// The activity map of a bit block whose width is a multiple of 64 (life_act.h;
+// LIFE_OPT_SKIP_DEAD): zeroes `map` (act_cols x act_rows cells of kActWords
+// row masks) and sets the bits of every owned row that holds a live cell.
+hipError_t launch_act_scan(const life_layout &L, const uint8_t *buf, uint32_t *map, hipStream_t s);
+
 // Copy-ceiling probe: out[0, bytes) = in[0, bytes), bytes a multiple of 16.
 hipError_t launch_copy(const void *in, void *out, int64_t bytes, hipStream_t s);
 

@@ -4,6 +4,7 @@
 // of them is near the roofline; they live apart from life_kernels.hip so that
 // a new output format does not touch the stencil's code object.
 #include "life_io.h"
+#include "life_act.h"
 #include "life_bitops.h"
 
 #include <stdint.h>
@@ -603,6 +604,37 @@ __global__ __launch_bounds__(256) void density_kernel(const uint8_t *buf, const 
     }
 }
 
+// Activity map of a bit buffer (LIFE_OPT_SKIP_DEAD, life_act.h): bit y % 32 of
+// the masks of map cell (y / 32, c) is set when owned row y holds a live cell
+// in pairs [62 c, 62 c + 62) / in the first / in the last of them; the map
+// arrives zeroed.  Shaped like the census: one streaming pass over the owned
+// cells only (w a multiple of 64: whole pairs), a lane per pair and an 8-B
+// load per row.  A workgroup per map cell, its four waves 8 rows each, one
+// ballot per row; a wave ORs in the masks of its rows.
+__global__ __launch_bounds__(256) void act_scan_kernel(const uint8_t *buf, const BlockView blk, uint32_t *map,
+                                                       int64_t ncol) {
+    const auto [pitch, ya, xoff, w, h, units, gx0, gy0] = blk;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r = blockIdx.x, c = blockIdx.y, W = w / 64;
+    const int64_t j = c * kActPairs + lane;
+    const bool on = lane < kActPairs && j < W;
+    const int llast = (int)(W - c * kActPairs < kActPairs ? W - c * kActPairs : kActPairs) - 1;
+    uint32_t m[kActWords] = {};
+    for (int k = 0; k < 8; ++k) {
+        const int64_t y = r * kActRows + 8 * wave + k;
+        if (y >= h) break;  // uniform
+        const uint64_t v = on ? *reinterpret_cast<const uint64_t *>(buf + (y + ya) * pitch + xoff + 8 * j) : 0ull;
+        const unsigned long long nz = __ballot(v != 0ull);
+        const uint32_t bit = 1u << (8 * wave + k);
+        if (nz) m[kActAny] |= bit;
+        if (nz & 1ull) m[kActFirst] |= bit;
+        if ((nz >> llast) & 1ull) m[kActLast] |= bit;
+    }
+    if (lane == 0)
+        for (int k = 0; k < kActWords; ++k)
+            if (m[k]) atomicOr(map + act_word(r, c, ncol, k), m[k]);
+}
+
 // Copy ceiling: one 16-B load + store per lane, one wave-instruction each,
 // a workgroup per 4 KiB.  Measured against grid-stride, unrolled and
 // nontemporal variants (scripts/ubench_copy.hip, profiles/r01/ubench_copy.txt):
@@ -717,6 +749,16 @@ hipError_t launch_paste_piece(const life_layout &L, uint8_t *buf, int64_t lx0, i
     const int64_t lanes = is_bit(L) ? ((lx0 + pw - 1) >> 6) - (lx0 >> 6) + 1 : pw;  // pairs touched / cells
     const dim3 grid(blocks_for(lanes, 256), (unsigned)(ph < 8192 ? ph : 8192));
     return launch_enc(L, paste_kernel<true>, paste_kernel<false>, grid, s, buf, view(L), lx0, ly0, pw, ph, in, ipitch);
+}
+
+hipError_t launch_act_scan(const life_layout &L, const uint8_t *buf, uint32_t *map, hipStream_t s) {
+    if (!is_bit(L) || L.w % 64 != 0) return hipErrorInvalidValue;
+    const int64_t ncol = act_cols(L.w / 64), nrow = act_rows(L.h);
+    if (ncol > 65535 || nrow > 0x7fffffff) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(map, 0, (size_t)(ncol * nrow * kActWords) * sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    act_scan_kernel<<<dim3((unsigned)nrow, (unsigned)ncol), 256, 0, s>>>(buf, view(L), map, ncol);
+    return hipGetLastError();
 }
 
 hipError_t launch_density(const life_layout &L, const uint8_t *buf, int64_t fx, int64_t fy, int64_t bw,

@@ -134,6 +134,19 @@ hipError_t launch_tstep(const life_layout &L, const uint8_t *in, uint8_t *out, c
                         int m, Wrap wrap, hipStream_t s,
                         double *valu_lane_ops = nullptr, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
                         Extend ext = Extend{}, int64_t concurrent = 0, const RuleWords *rule = nullptr);
+// One skip-dead pass (LIFE_OPT_SKIP_DEAD) of m generations over a single bit
+// shard whose axes both wrap in the stencil (w a multiple of 64), three
+// stream-ordered steps on `s`: the plan kernel classes every tile of the
+// plain tile grid from `src_map` (the activity map of `in`, life_act.h) and
+// the old `dst_map` (that of `out`) into cls[0, skip_tiles(L, m)) and adds
+// the counts of tiles run / cleared / skipped to cnt[0..2]; dst_map is
+// zeroed; the tile launch runs, clears or skips each tile and marks in
+// dst_map what it stored.  `rule`: as launch_tstep.
+int64_t skip_tiles(const life_layout &L, int m);  // tiles of such a pass (grows as m does)
+int64_t act_map_bytes(const life_layout &L);      // one buffer's activity map
+hipError_t launch_tskip(const life_layout &L, const uint8_t *in, uint8_t *out, int m, const uint32_t *src_map,
+                        uint32_t *dst_map, uint8_t *cls, unsigned long long *cnt, hipStream_t s,
+                        const RuleWords *rule = nullptr);
 // Computes (and caches) the launch-tail plans launch_tstep will use for the
 // whole-shard launches of layout L at m = 1 .. mmax generations (with
 // ext_y: also every deep-halo extension 0 .. K - m), so that a step call

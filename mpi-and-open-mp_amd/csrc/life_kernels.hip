@@ -25,6 +25,7 @@
 //    the same bit kernels: the rule is a compile-time policy on the shared
 //    bodies (ConwayRule / TableRule, life_bitops.h), 2 x 25 for the rule.
 #include "life_kernels.h"
+#include "life_act.h"
 #include "life_bitops.h"
 #include "life_diag.h"
 #include "life_env.h"
@@ -474,13 +475,22 @@ struct XchB {
 #define LIFE_FAST_WRAP 1
 #endif
 
-template <int R, bool WRAPX, bool WRAPY, int FLOW, int NW, bool BAND = false, class RP = ConwayRule>
+//
+// ACT (tskip kernels, LIFE_OPT_SKIP_DEAD): a plain tile also notes, per row it
+// stores, whether any lane, the lane of its first pair or the lane of its last
+// pair stored a set bit (one ballot per row: wave-uniform masks in SGPRs), and
+// one lane ORs the masks into `act`, the zeroed map of the output buffer
+// (life_act.h: R <= kActRows rows of a wave lie in at most two map rows, all in
+// map column tx).  Compiles to nothing when off: the other instances keep
+// their code.
+template <int R, bool WRAPX, bool WRAPY, int FLOW, int NW, bool BAND = false, class RP = ConwayRule, bool ACT = false>
 __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in, uint8_t *out, int64_t tx,
                                               int64_t ty, XchB<NW> &xb, int gsh = 6, int nb = 1,
                                               int64_t ybase = 0, int64_t yend = -1, int64_t org = 0, int own = 62,
-                                              const RP &rule = RP{}) {
+                                              const RP &rule = RP{}, uint32_t *act = nullptr) {
     XchP<NW> &xch = xb.s;
     static_assert(R >= 3, "window");
+    static_assert(!ACT || (!BAND && !FLOW && R <= kActRows), "activity map: plain tiles");
     const int K = a.m;  // ghost rows per window end
     const int T = NW * R - 2 * K;
     const int lane = threadIdx.x & 63;
@@ -657,6 +667,10 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
     const int64_t yb = y0 + (BAND ? (int64_t)(gl2 < nb ? gl2 : 0) * T : 0);  // this lane's band
     const int64_t ylim = yend >= 0 ? yend : a.h;  // half tiles of a region stop at its last row
     uint8_t *q = out + (a.ya + yb + r0) * a.pitch + voff;
+    // ACT: the row masks (life_act.h) of what this wave stores in map rows ar0 and ar0 + 1, wave-uniform
+    uint32_t am[2][kActWords] = {};
+    const int64_t ar0 = ACT ? (yb + r0) / kActRows : 0;
+    const int llast = ACT ? (int)min((int64_t)kActPairs, a.W - tx * kActPairs) : 0;  // lane of the last owned pair
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         if (r < r0 || r >= r1) continue;
@@ -667,7 +681,25 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
             else
                 *reinterpret_cast<uint64_t *>(q) = v;
         }
+        if (ACT && yb + r < ylim) {  // (uniform: every lane of the wave is here)
+            const unsigned long long nz = __ballot(st && (ve[r] | vo[r]) != 0u);
+            const uint32_t bit = 1u << ((yb + r) % kActRows);
+            const int k = (yb + r) / kActRows == ar0 ? 0 : 1;
+            if (nz) am[k][kActAny] |= bit;
+            if ((nz >> 1) & 1ull) am[k][kActFirst] |= bit;  // lane 1 holds pair 62 tx
+            if ((nz >> llast) & 1ull) am[k][kActLast] |= bit;
+        }
         q += a.pitch;
+    }
+    if (ACT && lane2 == 0) {
+        // stored rows are owned rows (< h): a nonzero mask's map row exists.  Waves (24 rows) and
+        // vertically adjacent tiles share 32-row words: OR, not store.
+        const int64_t ncol = act_cols(a.W);
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int w = 0; w < kActWords; ++w)
+                if (am[k][w]) atomicOr(act + act_word(ar0 + k, tx, ncol, w), am[k][w]);
     }
 }
 
@@ -964,6 +996,91 @@ template <int R, bool WRAPX, bool WRAPY, int NW>
 __global__ __launch_bounds__(64 * NW, LIFE_RULE_WPE) void trule_bit_kernel(RTArgs a) {
     __shared__ XchB<NW> xch;
     tstep_bit_body<R, WRAPX, WRAPY, NW>(a.t, xch, TableRule(a.w));
+}
+
+// ---- skip-dead passes (LIFE_OPT_SKIP_DEAD; DESIGN.md 5.9, life_act.h)
+// A pass over a single shard whose axes both wrap in the stencil runs only
+// the tiles whose input window may hold a live cell: nothing is born from
+// nothing (B0 rules are refused), so a tile whose window is dead produces a
+// dead block.  Three stream-ordered steps per pass (launch_tskip):
+//  1. act_plan_kernel, a thread per tile of the plain tile grid (no banded
+//     column, no tail split): the tile is kActRun if any cell of the input
+//     buffer's map under its window is set, else kActClear if any cell of the
+//     output buffer's OLD map under its owned rows is set, else kActSkip; the
+//     three counts go to the call's counters;
+//  2. the output buffer's map is zeroed (only now: step 1 has read it);
+//  3. tskip_*_kernel, a workgroup per tile, reads its class before anything
+//     else: kActSkip returns (the whole workgroup, before any barrier),
+//     kActClear stores zeros over its owned rows and pairs and nothing else,
+//     kActRun is tile_body_bit as a plain tile with the ACT flag.
+struct PlanArgs {
+    const uint32_t *src_map, *dst_map;
+    uint8_t *cls;
+    unsigned long long *cnt;  // run, cleared, skipped
+    int64_t W, h, T, ntx, nty;
+    int32_t m;
+};
+__global__ __launch_bounds__(256) void act_plan_kernel(PlanArgs p) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int c = -1;  // past the last tile
+    if (i < p.ntx * p.nty) {
+        const int64_t tx = i % p.ntx, ty = i / p.ntx;
+        if (act_window_live(p.src_map, p.W, act_read_rows(ty, p.T, p.m, p.h), tx))
+            c = kActRun;
+        else if (act_own_live(p.dst_map, p.W, act_own_rows(ty, p.T, p.h), tx))
+            c = kActClear;
+        else
+            c = kActSkip;
+        p.cls[i] = (uint8_t)c;
+    }
+    const unsigned long long run = __ballot(c == kActRun), clr = __ballot(c == kActClear),
+                             skp = __ballot(c == kActSkip);
+    if ((threadIdx.x & 63) == 0) {
+        if (run) atomicAdd(p.cnt, (unsigned long long)__popcll(run));
+        if (clr) atomicAdd(p.cnt + 1, (unsigned long long)__popcll(clr));
+        if (skp) atomicAdd(p.cnt + 2, (unsigned long long)__popcll(skp));
+    }
+}
+
+struct KArgs {
+    TArgs t;
+    const uint8_t *cls;  // class per tile, row-major over ntx x nty
+    uint32_t *act;       // the output buffer's map, zeroed
+    int64_t ntx, nty;
+};
+template <int R, int NW, class RP>
+__device__ __forceinline__ void tskip_body(const KArgs &k, XchB<NW> &xch, const RP &rule) {
+    const TArgs &a = k.t;
+    const int64_t wg = blockIdx.x;
+    if (wg >= k.ntx * k.nty) return;
+    const int c = __builtin_amdgcn_readfirstlane((int)k.cls[wg]);
+    if (c == kActSkip) return;  // whole workgroup, uniform, before any barrier
+    const int64_t tx = wg % k.ntx, ty = wg / k.ntx;
+    if (c == kActClear) {
+        const int64_t T = (int64_t)NW * R - 2 * a.m;
+        const int64_t ya = ty * T, yb = act_own_end(ty, T, a.h);
+        const int lane = threadIdx.x & 63;
+        const int64_t j = tx * kActPairs + lane;
+        if (lane < kActPairs && j < a.W)
+            for (int64_t y = ya + (threadIdx.x >> 6); y < yb; y += NW)
+                *reinterpret_cast<uint64_t *>(a.out + (a.ya + y) * a.pitch + a.xoff + 8 * j) = 0ull;
+        return;
+    }
+    tile_body_bit<R, true, true, 0, NW, false, RP, true>(a, a.in, a.out, tx, ty, xch, 6, 1, 0, -1, 0, 62, rule, k.act);
+}
+template <int R, int NW>
+__global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tskip_bit_kernel(KArgs k) {
+    __shared__ XchB<NW> xch;
+    tskip_body<R, NW>(k, xch, ConwayRule{});
+}
+struct RKArgs {
+    KArgs k;
+    RuleWords w;
+};
+template <int R, int NW>
+__global__ __launch_bounds__(64 * NW, LIFE_RULE_WPE) void tskip_rule_kernel(RKArgs a) {
+    __shared__ XchB<NW> xch;
+    tskip_body<R, NW>(a.k, xch, TableRule(a.w));
 }
 
 template <int R, int GK, bool WRAPX, bool WRAPY, int NW>
@@ -1893,6 +2010,67 @@ hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out,
                                             : byte_k<32>(wrap);
     if (!fn) return hipErrorInvalidValue;
     return launch_fn(fn, (unsigned)items, 64u * (unsigned)tile_waves(bit), &a, s, ev0, ev1);
+}
+
+namespace {
+const void *skip_k(bool rule) {
+    const int R = temporal_rows(true), NW = tile_waves(true);
+#define LIFE_BIT_CASE(r, nw) \
+    if (R == r && NW == nw) return rule ? (const void *)tskip_rule_kernel<r, nw> : (const void *)tskip_bit_kernel<r, nw>;
+    LIFE_BIT_SHAPES(LIFE_BIT_CASE)
+#undef LIFE_BIT_CASE
+    return nullptr;
+}
+}  // namespace
+
+int64_t act_map_bytes(const life_layout &L) {
+    return act_cols((L.w + 63) / 64) * act_rows(L.h) * kActWords * (int64_t)sizeof(uint32_t);
+}
+
+int64_t skip_tiles(const life_layout &L, int m) {
+    const int64_t T = (int64_t)tile_waves(true) * temporal_rows(true) - 2 * (int64_t)m;
+    if (!is_bit(L) || T < 1) return 0;
+    return act_cols((L.w + 63) / 64) * ((L.h + T - 1) / T);
+}
+
+hipError_t launch_tskip(const life_layout &L, const uint8_t *in, uint8_t *out, int m, const uint32_t *src_map,
+                        uint32_t *dst_map, uint8_t *cls, unsigned long long *cnt, hipStream_t s,
+                        const RuleWords *rule) {
+    const int K = L.generations_per_exchange;
+    const int64_t T = (int64_t)tile_waves(true) * temporal_rows(true) - 2 * (int64_t)m;
+    // both axes wrap in the stencil: whole pairs, no apron to fill
+    if (!is_bit(L) || m < 1 || m > K || m > 32 || K < 2 || L.yapron != K || T < 1 || L.w % 64 != 0)
+        return hipErrorInvalidValue;
+    KArgs k{};
+    TArgs &a = k.t;
+    a.in = in;
+    a.out = out;
+    a.pitch = L.pitch;
+    a.xoff = L.xoff;
+    a.W = L.w / 64;
+    a.h = L.h;
+    a.ya = L.yapron;
+    a.m = m;
+    a.btx1 = -1;  // plain tiles: no banded column, no tail split, dispatch order
+    k.ntx = act_cols(a.W);
+    k.nty = (L.h + T - 1) / T;
+    k.cls = cls;
+    k.act = dst_map;
+    const int64_t tiles = k.ntx * k.nty;
+    if (tiles > 0x7fffffff) return hipErrorInvalidValue;
+    PlanArgs p{src_map, dst_map, cls, cnt, a.W, a.h, T, k.ntx, k.nty, m};
+    act_plan_kernel<<<(unsigned)((tiles + 255) / 256), 256, 0, s>>>(p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(dst_map, 0, (size_t)act_map_bytes(L), s);
+    if (e != hipSuccess) return e;
+    const void *fn = skip_k(rule != nullptr);
+    if (!fn) return hipErrorInvalidValue;
+    if (rule) {
+        RKArgs ra{k, *rule};
+        return launch_fn(fn, (unsigned)tiles, 64u * (unsigned)tile_waves(true), &ra, s, nullptr, nullptr);
+    }
+    return launch_fn(fn, (unsigned)tiles, 64u * (unsigned)tile_waves(true), &k, s, nullptr, nullptr);
 }
 
 namespace {

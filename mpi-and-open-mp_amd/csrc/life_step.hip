@@ -9,6 +9,7 @@
 #include <chrono>
 #include <utility>
 
+#include "life_act.h"
 #include "life_dev_internal.h"
 #include "life_env.h"
 
@@ -576,8 +577,78 @@ void note_pass(life_dev *d, std::chrono::steady_clock::time_point t0) {
     if (ms > d->call_pass_max_ms) d->call_pass_max_ms = ms;
 }
 
+// ---- skip-dead passes (LIFE_OPT_SKIP_DEAD; DESIGN.md 5.9, life_act.h)
+// The device runs its passes this way: the option on, a single shard in a
+// single process, both axes wrapped by the stencil (so w % 64 == 0), the bit
+// encoding, a temporal layout, not the small-grid path.  Any rule
+// life_dev_set_rule accepts (none is B0).
+bool skip_dead_applies(const life_dev *d) {
+    return d->skip_dead && d->shards.size() == 1 && d->world == 1 && !part(d, 0) && !part(d, 1) && !self_wrap_x(d) &&
+           d->kernel == LIFE_KERNEL_BIT && temporal(d) && !small_grid(d);
+}
+
+// The shard's maps and counters (once), and room for the classes of `tiles` tiles.
+int act_scratch(Shard &s, int64_t tiles) {
+    const size_t bytes = (size_t)life::act_map_bytes(s.lay);
+    if (!s.act_map[0]) {
+        HIPCHK(hipMalloc(&s.act_map[0], 2 * bytes));
+        s.act_map[1] = s.act_map[0] + bytes / sizeof(uint32_t);
+    }
+    if (!s.act_cnt) HIPCHK(hipMalloc(&s.act_cnt, 3 * sizeof(unsigned long long)));
+    if ((size_t)tiles > s.act_cls_cap) {
+        if (s.act_cls) HIPCHK(hipFree(s.act_cls));  // (waits for the device: no queued pass still reads it)
+        s.act_cls = nullptr;
+        s.act_cls_cap = 0;
+        HIPCHK(hipMalloc(&s.act_cls, (size_t)tiles));
+        s.act_cls_cap = (size_t)tiles;
+    }
+    return LIFE_OK;
+}
+
+// A step call of skip-dead passes on the single shard, all on its compute
+// stream; nothing is read back and nothing waited for.  Invalid maps (an
+// edit, a pass of another form or the option switched on since the last such
+// pass) are rebuilt first: one streaming scan of the current buffer, and all
+// ones for the other one, whose content is unknown (0xA5 on a fresh device
+// under LIFE_POISON=1), so the first pass clears whatever it does not run.
+int step_skip(life_dev *d, int64_t generations) {
+    Shard &s = d->shards[0];
+    const life_layout &L = s.lay;
+    HIPCHK(hipSetDevice(s.device));
+    const int K = L.generations_per_exchange, bmax = max_pass_gens(d);
+    CHK(act_scratch(s, life::skip_tiles(L, bmax)));  // the shortest tiles of the call: the most
+    HIPCHK(hipMemsetAsync(s.act_cnt, 0, 3 * sizeof(unsigned long long), s.stream));
+    if (!d->act_valid) {
+        HIPCHK(life::launch_act_scan(L, s.buf[s.cur], s.act_map[s.cur], s.stream));
+        HIPCHK(hipMemsetAsync(s.act_map[s.cur ^ 1], 0xFF, (size_t)life::act_map_bytes(L), s.stream));
+        d->act_valid = true;
+    }
+    d->last_path = LIFE_PATH_SKIP;
+    for (int64_t g = 0; g < generations;) {
+        const life::PassPlan p = life::next_pass(K, bmax, false, d->since, generations - g);
+        const auto t0 = std::chrono::steady_clock::now();
+        // one timed launch: the plan, the map clear and the tiles under one
+        // bracket; the whole grid's cell-updates, but no bytes and no VALU ops
+        // (the host does not know how many tiles ran: life_dev_activity)
+        Bracket b;
+        CHK(bracket_begin(d, s, true, 1, kExtNever, false, s.stream, &b));
+        HIPCHK(life::launch_tskip(L, s.buf[s.cur], s.buf[s.cur ^ 1], p.m, s.act_map[s.cur], s.act_map[s.cur ^ 1],
+                                  s.act_cls, s.act_cnt, s.stream, rule_of(d)));
+        CHK(bracket_end(b, s.stream));
+        if (b.t) book(d, true, (double)L.w * (double)L.h, (double)p.m, 0.0, 0.0);
+        s.cur ^= 1;
+        d->act_passes++;
+        d->act_total += life::skip_tiles(L, p.m);
+        note_pass(d, t0);
+        g += p.m;
+    }
+    return LIFE_OK;
+}
+
 // The launches of one step call (life_dev_step after its entry fence).
 int step_body(life_dev *d, int64_t generations) {
+    if (skip_dead_applies(d)) return step_skip(d, generations);
+    d->act_valid = false;  // a pass of any other form leaves the activity maps behind
     if (small_grid(d)) {
         d->last_path = LIFE_PATH_SMALL;
         constexpr int64_t kChunk = 1 << 20;  // generations per resident launch
@@ -619,7 +690,7 @@ int step_body(life_dev *d, int64_t generations) {
 // behind the dataflow form's share; no plan for the first pass's tile grid.
 int pipe_regions(const life_dev *d, int64_t generations) {
     if (d->pipe == 0 || d->shards.size() != 1 || d->world != 1 || part(d, 0) || part(d, 1) || self_wrap_x(d) ||
-        !temporal(d) || small_grid(d))
+        !temporal(d) || small_grid(d) || skip_dead_applies(d))  // (skip-dead passes run whole, on one stream)
         return 0;
     if (d->timing && d->launch_events && timing_mode() != kTimeCall && timing_mode() != kTimeOff) return 0;
     int form = 0, fm = 0;
@@ -748,11 +819,29 @@ int life_dev_step(life_dev *d, int64_t generations) {
     d->call_passes = 0;
     d->call_pass_max_ms = 0.0;
     d->call_spans = false;
+    d->act_passes = d->act_total = 0;
     const int rc = step_call(d, generations);
     d->call_host_ms = ms_since(t0);
     return rc;
 }
 
 int life_dev_last_path(life_dev *d) { return d ? d->last_path : LIFE_EINVAL; }
+
+int life_dev_activity(life_dev *d, int64_t *passes, int64_t *tiles_run, int64_t *tiles_cleared, int64_t *tiles_total) {
+    if (!d) return LIFE_EINVAL;
+    unsigned long long cnt[3] = {0, 0, 0};
+    if (d->act_passes > 0) {
+        CHK(life_dev_sync(d));
+        Shard &s = d->shards[0];
+        HIPCHK(hipSetDevice(s.device));
+        HIPCHK(hipMemcpyAsync(cnt, s.act_cnt, sizeof cnt, hipMemcpyDeviceToHost, s.stream));
+        HIPCHK(hipStreamSynchronize(s.stream));
+    }
+    if (passes) *passes = d->act_passes;
+    if (tiles_run) *tiles_run = (int64_t)cnt[0];
+    if (tiles_cleared) *tiles_cleared = (int64_t)cnt[1];
+    if (tiles_total) *tiles_total = d->act_total;
+    return LIFE_OK;
+}
 
 }  // extern "C"

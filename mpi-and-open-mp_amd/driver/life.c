@@ -31,6 +31,12 @@
  *                     grid is never allocated; same cells, same frames.  With
  *                     --format density a pattern in a 65536^2 universe needs
  *                     kilobytes on the host
+ *   --skip-dead       step only the tiles whose window may hold a live cell
+ *                     (LIFE_OPT_SKIP_DEAD, set before the first step): the run
+ *                     time follows the pattern, not the universe; same frames
+ *                     and dumps.  Independent of --sparse, which is I/O only;
+ *                     no effect where the device does not qualify (byte
+ *                     kernel, several GPUs, a width that is no multiple of 64)
  *   --resume FILE     start from a .bits dump instead of the .cfg cells: the
  *                     dump sets nx and ny and goes to the device packed
  *                     (life_dev_upload_bits); frames continue its numbering
@@ -346,7 +352,7 @@ static uint8_t *unpack_bits(const uint8_t *packed, int64_t w, int64_t h) {
 int main(int argc, char **argv) {
     const char *cfg_path = NULL, *resume = NULL;
     int gpus = 1, kernel = LIFE_KERNEL_BIT, vtk = 1, live = 0, have_random = 0, bits = 0, force_rank = 0;
-    int partition = LIFE_PARTITION_CART, sparse = 0, have_at = 0;
+    int partition = LIFE_PARTITION_CART, sparse = 0, have_at = 0, skip_dead = 0;
     long long at_x = 0, at_y = 0; /* --at X,Y */
     long long dfx = 0, dfy = 0; /* --format density:FX[xFY] (bits == 2) */
     long long o_nx = -1, o_ny = -1, o_steps = -1, o_save = -1;
@@ -396,6 +402,7 @@ int main(int argc, char **argv) {
                 bits = !*end && end != fm + 8 && dfx >= 1 && dfy >= 1 ? 2 : -1;
             }
         } else if (!strcmp(s, "--sparse")) sparse = 1;
+        else if (!strcmp(s, "--skip-dead")) skip_dead = 1;
         else if (!strcmp(s, "--resume") && more) resume = argv[++a];
         else if (!strcmp(s, "--at") && more) {
             char *end;
@@ -520,6 +527,7 @@ int main(int argc, char **argv) {
     }
     if (rc) die("create", rc);
     if (have_rule && (rc = life_dev_set_rule(d, birth, survive)) != LIFE_OK) die("--rule", rc);
+    if (skip_dead && (rc = life_dev_configure(d, LIFE_OPT_SKIP_DEAD, 1)) != LIFE_OK) die("--skip-dead", rc);
     const int writer = !rank_mode || rank == root; /* the process that writes frames and prints */
     uint8_t *grid = NULL; /* packed rows: bits frames */
     char *body = NULL;    /* VTK cell text */

@@ -46,6 +46,7 @@ OPT_SMALL_GRID, OPT_OVERLAP, OPT_SMALL_WINDOW, OPT_BLOCK_GENS, OPT_LOOPBACK, OPT
 OPT_FLOW_CHUNK = 8
 OPT_DEEP_HALO = 9
 OPT_PIPELINE = 11  # 0 off, 1 automatic, 3..16 row regions per pass (LIFE_OPT_PIPELINE)
+OPT_SKIP_DEAD = 12  # 0 off, 1 run only the tiles whose window may hold a live cell (LIFE_OPT_SKIP_DEAD)
 # LIFE_TEMPORAL_DEPTH(_BYTE): generations per halo exchange of the temporal layouts
 TEMPORAL_DEPTH = {"bit": 32, "byte": 32}
 BLOCK_GENS = {"bit": 12, "byte": 32}  # tiles: default generations per launch at most (LIFE_OPT_BLOCK_GENS)
@@ -73,8 +74,9 @@ ABI_SYMBOLS = (
     "life_dev_clear", "life_dev_set_cells", "life_dev_gather_rect", "life_dev_gather_density",
     "life_dev_upload_bits", "life_dev_set_rect",
     "life_rule_parse", "life_rule_format", "life_dev_set_rule", "life_dev_get_rule",
+    "life_dev_activity",
 )
-PATHS = {0: "none", 1: "onegen", 2: "tiles", 3: "flow", 5: "small"}
+PATHS = {0: "none", 1: "onegen", 2: "tiles", 3: "flow", 5: "small", 6: "skip"}
 
 
 class LifeError(RuntimeError):
@@ -183,6 +185,8 @@ def _lib():
             L.life_rule_format.argtypes = [u32, u32, ctypes.c_char_p]
             L.life_dev_set_rule.argtypes = [vp, u32, u32]
             L.life_dev_get_rule.argtypes = [vp, P(u32), P(u32)]
+        if hasattr(L, "life_dev_activity"):  # absent from builds that predate LIFE_OPT_SKIP_DEAD (A/B runs)
+            L.life_dev_activity.argtypes = [vp] + [P(i64)] * 4
         L.life_tune.argtypes = [i32, i32, i32]
         L.life_tune_temporal.argtypes = [i32, i32]
         L.life_measure_copy.argtypes = [i32, i64, i32, P(ctypes.c_double)]
@@ -325,7 +329,7 @@ class Life:
 
     def __init__(self, nx: int, ny: int, shards: int = 1, kernel="bit", dims=(0, 0),
                  transport: int = XPORT_AUTO, small_grid: bool = True, overlap: bool = True, flow=None,
-                 window=None, rule=None, _handle=None):
+                 window=None, rule=None, skip_dead: bool = False, _handle=None):
         self.nx, self.ny = int(nx), int(ny)
         self.kernel = kernel_id(kernel)
         self._h = ctypes.c_void_p()
@@ -355,6 +359,10 @@ class Life:
         # rule: None (B3/S23), a rulestring or a (birth, survive) pair (set_rule)
         if rule is not None:
             self.set_rule(rule)
+        # skip_dead: run only the tiles whose window may hold a live cell
+        # (LIFE_OPT_SKIP_DEAD; no effect on devices that do not qualify)
+        if skip_dead:
+            self.configure(OPT_SKIP_DEAD, 1)
 
     def configure(self, option: int, value: int) -> None:
         _check(_lib().life_dev_configure(self._h, option, value), "configure")
@@ -530,6 +538,14 @@ class Life:
     def last_path(self) -> str:
         """Kernel family of the last step call (life_dev_last_path)."""
         return PATHS[_check(_lib().life_dev_last_path(self._h), "last_path")]
+
+    def activity(self):
+        """(passes, tiles_run, tiles_cleared, tiles_total) summed over the
+        skip-dead passes of the last step call (life_dev_activity; blocking);
+        zeros when it ran none."""
+        v = [ctypes.c_int64() for _ in range(4)]
+        _check(_lib().life_dev_activity(self._h, *[ctypes.byref(x) for x in v]), "activity")
+        return tuple(x.value for x in v)
 
     def flow_active(self) -> bool:
         return self.last_path() == "flow"
