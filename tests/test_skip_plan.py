@@ -26,6 +26,12 @@ rows at m = 12, the last partial) at m = 12, 10, 5, 1; 3968 x 1349 at m = 12,
 whose last tile row has 5 rows, fewer than m, so tile row 0's window reaches
 two tile rows up; 4096 x 200 and 3968 x 160, where a tile is its own
 neighbour (the latter one tile in all).
+
+The window height is a parameter: 192 rows (8 waves x 24 register rows, the
+default shape; also at m = 16, 17 and 32) and 128 rows (16 register rows):
+T = 128 - 2m is 104 at m = 12, 64 at m = 32; 3968 x 1253 has a 5-row last tile
+row there; 4032 wide leaves one pair to the last map column, 64 wide is one
+pair in all, 3968 x 5 is lower than one map row.
 """
 import os
 import subprocess
@@ -81,9 +87,29 @@ int main(int argc, char **argv) {
 }
 """
 
-WINDOW = 8 * 24  # rows of a tile's window: 8 waves x 24 register rows
+WINDOW = 8 * 24  # rows of a tile's window: 8 waves x 24 register rows (the default shape)
+WINDOW16 = 8 * 16  # ... x 16 register rows (life_tune_temporal / LIFE_TEMPORAL_ROWS 16)
 GEOMS = [(8192, 700, 12), (8192, 700, 10), (8192, 700, 5), (8192, 700, 1), (3968, 1349, 12), (4096, 200, 12),
          (4096, 200, 1), (3968, 160, 12)]
+
+
+def shaped(window, cases):
+    """(nx, ny, m, window) parameters, ids 'w<window>-nx-ny-m'."""
+    return [pytest.param(*c, window, id="w%d-%d-%d-%d" % ((window,) + c)) for c in cases]
+
+
+def default_shape(cases):
+    return [pytest.param(*c, WINDOW, id="%d-%d-%d" % c) for c in cases]
+
+
+# m above 16: at 16-row waves whole waves of the window are ghost; at m = 32 a 128-row window owns 64 rows, two
+# map rows; T = 128 - 2m is 104, 106, 94: another alignment against the map's 32-row words; 3968 x 1253 at
+# T = 104: a last tile row of 5 rows, fewer than m; one pair in the last map column (4032), one pair in all (64:
+# a column its own left and right neighbour), a height under one map row (3968 x 5); 8000: three map columns,
+# the last of one pair (4032 has two, and its last is both neighbours of its first)
+GEOMS_DEEP = [(8192, 700, 16), (8192, 700, 17), (8192, 700, 32)]
+GEOMS16 = [(8192, 700, 12), (8192, 700, 11), (8192, 700, 17), (8192, 700, 32), (3968, 1253, 12), (4032, 200, 12),
+           (64, 40, 12), (3968, 5, 12), (8000, 200, 12)]
 
 
 @pytest.fixture(scope="module")
@@ -108,9 +134,9 @@ def row_set(tok, i):
     return rows, cells, i + 1 + 2 * n
 
 
-def plan(exe, nx, ny, m, mapfile=None):
+def plan(exe, nx, ny, m, mapfile=None, window=WINDOW):
     """{(tx, ty): dict} and (ncol, nrow)."""
-    W, T = nx // 64, WINDOW - 2 * m
+    W, T = nx // 64, window - 2 * m
     cmd = [exe, str(W), str(ny), str(T), str(m)] + ([mapfile] if mapfile else [])
     lines = subprocess.run(cmd, capture_output=True, text=True, check=True).stdout.splitlines()
     g = lines[0].split()
@@ -128,10 +154,12 @@ def plan(exe, nx, ny, m, mapfile=None):
     return tiles, (int(g[4]), int(g[5]))
 
 
-@pytest.mark.parametrize("nx,ny,m", GEOMS)
-def test_read_and_owned_sets_match_brute_force(harness, nx, ny, m):
-    W, T = nx // 64, WINDOW - 2 * m
-    tiles, (ncol, nrow) = plan(harness, nx, ny, m)
+@pytest.mark.parametrize("nx,ny,m,window",
+                         default_shape(GEOMS) + shaped(WINDOW, GEOMS_DEEP) + shaped(WINDOW16, GEOMS16))
+def test_read_and_owned_sets_match_brute_force(harness, nx, ny, m, window):
+    W, T = nx // 64, window - 2 * m
+    assert T > 0
+    tiles, (ncol, nrow) = plan(harness, nx, ny, m, window=window)
     ntx, nty = -(-W // 62), -(-ny // T)
     assert (ncol, nrow) == (ntx, -(-ny // 32))
     assert sorted(tiles) == sorted((tx, ty) for ty in range(nty) for tx in range(ntx))
@@ -161,11 +189,11 @@ def test_short_last_tile_row_reaches_two_tile_rows_up(harness):
     assert tiles[(0, 8)]["own"] == set(range(1344, 1349))
 
 
-def sparse_state(nx, ny, seed):
-    """A few 6 x 6 soups, some straddling the tile corners and the periodic corner."""
+def sparse_state(nx, ny, seed, corner_y=168):
+    """A few 6 x 6 soups, some straddling the tile corner (3968, corner_y) and the periodic corner."""
     rng = np.random.default_rng(seed)
     g = np.zeros((ny, nx), np.uint8)
-    spots = [(3968 % nx - 3, 168 % ny - 3), (nx - 3, ny - 3), (int(rng.integers(nx)), int(rng.integers(ny))),
+    spots = [(3968 % nx - 3, corner_y % ny - 3), (nx - 3, ny - 3), (int(rng.integers(nx)), int(rng.integers(ny))),
              (int(rng.integers(nx)), int(rng.integers(ny)))]
     for x, y in spots[seed % 2:]:
         blob = (rng.random((6, 6)) < 0.5).astype(np.uint8)
@@ -189,16 +217,19 @@ def activity_map(g, ncol, nrow):
     return words
 
 
-@pytest.mark.parametrize("nx,ny,m", [(8192, 700, 12), (8192, 700, 5), (3968, 1349, 12), (4096, 200, 12)])
-def test_model_pass_skips_only_dead_blocks(harness, oracle, tmp_path, nx, ny, m):
-    W, T = nx // 64, WINDOW - 2 * m
+@pytest.mark.parametrize("nx,ny,m,window",
+                         default_shape([(8192, 700, 12), (8192, 700, 5), (3968, 1349, 12), (4096, 200, 12)]) +
+                         shaped(WINDOW16, [(8192, 700, 12), (8192, 700, 32), (3968, 1253, 12)]))
+def test_model_pass_skips_only_dead_blocks(harness, oracle, tmp_path, nx, ny, m, window):
+    W, T = nx // 64, window - 2 * m
     skipped = ran = 0
     for seed in (1, 2, 3):
-        g = sparse_state(nx, ny, seed)
+        # (the default shape's cases keep their corner spot at row 168, whatever their m)
+        g = sparse_state(nx, ny, seed, 168 if window == WINDOW else T)
         ncol, nrow = -(-W // 62), -(-ny // 32)
         f = tmp_path / f"map{seed}.bin"
         activity_map(g, ncol, nrow).tofile(f)
-        tiles, _ = plan(harness, nx, ny, m, str(f))
+        tiles, _ = plan(harness, nx, ny, m, str(f), window=window)
         want = oracle.life_run(g, m)
         for (tx, ty), t in tiles.items():
             y0, y1 = ty * T, min(ty * T + T, ny)
