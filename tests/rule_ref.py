@@ -27,6 +27,28 @@ def rule_run(grid: np.ndarray, gens: int, rule) -> np.ndarray:
     return grid
 
 
+PARITY = NAMED["B1357/S1357"]  # the next state is the XOR of the eight neighbours: linear over GF(2)
+
+
+def parity_run(grid: np.ndarray, gens: int) -> np.ndarray:
+    """`gens` generations of PARITY on a periodic grid of any size, without
+    stepping.  One generation is the operator P = the XOR of the eight copies
+    of the grid rolled by one cell; over GF(2) squaring is linear, so P^(2^k)
+    is the XOR of the eight copies rolled by 2^k, and P^gens the product of
+    those over the set bits k of gens.  np.roll wraps at any size, so this
+    holds on widths and heights that are no powers of two (a roll by more than
+    the size, or two rolls that meet, are still what iterated steps give).
+    tests/test_light_cone_host.py pins it to rule_run."""
+    g = np.array(grid, dtype=np.uint8)
+    k = 1
+    while k <= gens:
+        if gens & k:
+            h = g ^ np.roll(g, k, 1) ^ np.roll(g, -k, 1)  # the 3 x 3 block at spacing k, rows first, then
+            g = h ^ np.roll(h, k, 0) ^ np.roll(h, -k, 0) ^ g  # minus the cell
+        k <<= 1
+    return g
+
+
 def conway_flips():
     """B3/S23 with one of its 18 table bits flipped, B0 excluded: 17 rules."""
     out = [(CONWAY[0] ^ (1 << k), CONWAY[1]) for k in range(1, 9)]

@@ -19,7 +19,11 @@ says.  Brute force over cells says what those must be:
 * the owned set is exactly the owned rows, in map column tx;
 * a model pass over random sparse states, the map built in numpy: every tile
   act_window_live does not run is all dead in the oracle's result after m
-  generations, and every tile whose cell window is dead is not run.
+  generations, and every tile whose cell window is dead is not run;
+* a model pass at light speed: those states move a row per two generations
+  at most, so under the parity rule (rule_ref.PARITY, one cell reaches
+  (+-m, +-m) in m generations) a single cell on a tile's diagonal makes the
+  tile run at distance m, and reaches its corner cell, and not at m + 1.
 
 Geometries: 8192 x 700 (three tile columns of 62, 62 and 4 pairs; five tile
 rows at m = 12, the last partial) at m = 12, 10, 5, 1; 3968 x 1349 at m = 12,
@@ -245,3 +249,38 @@ def test_model_pass_skips_only_dead_blocks(harness, oracle, tmp_path, nx, ny, m,
                 assert not want[y0:y1, x0:x1].any(), (seed, tx, ty)
     assert ran > 0
     assert skipped > 0 or len(tiles) <= 4
+
+
+@pytest.mark.parametrize("nx,ny,m", [(8192, 700, 12), (8192, 700, 32), (3968, 1349, 12)])
+def test_model_pass_at_light_speed(harness, tmp_path, nx, ny, m):
+    """The window is tight from both sides at c.  Every pattern above moves at most a row per two generations,
+    so a window of m / 2 ghost rows would pass.  Under the parity rule (rule_ref.PARITY) one cell is, m
+    generations on, alive at (+-m, +-m) whatever else the grid holds: for each tile, a single cell on the
+    exact diagonal north-west of its block's first cell and south-east of its last one, wraps included --
+    at distance m the tile must run, and rule_ref.parity_run puts a live cell into its block, namely that
+    corner; at distance m + 1 it must not run, and every tile that is not run is all dead after m
+    generations."""
+    import rule_ref
+
+    W, T = nx // 64, WINDOW - 2 * m
+    ncol, nrow = -(-W // 62), -(-ny // 32)
+    f = tmp_path / "map.bin"
+    g = np.zeros((ny, nx), np.uint8)
+    blocks = {(tx, ty): (ty * T, min(ty * T + T, ny), 64 * 62 * tx, min(64 * (62 * tx + 62), nx))
+              for ty in range(-(-ny // T)) for tx in range(ncol)}
+    for (tx, ty), (y0, y1, x0, x1) in blocks.items():
+        for cx, cy, sign in ((x0, y0, -1), (x1 - 1, y1 - 1, 1)):
+            for d in (m, m + 1):
+                x, y = (cx + sign * d) % nx, (cy + sign * d) % ny
+                g[y, x] = 1
+                activity_map(g, ncol, nrow).tofile(f)
+                tiles, _ = plan(harness, nx, ny, m, str(f))
+                want = rule_ref.parity_run(g, m)
+                g[y, x] = 0
+                where = (tx, ty, cx, cy, d)
+                assert tiles[(tx, ty)]["live"] == int(d == m), where
+                if d == m:
+                    assert want[cy, cx] == 1, where
+                for t, (b0, b1, a0, a1) in blocks.items():
+                    if not tiles[t]["live"]:
+                        assert not want[b0:b1, a0:a1].any(), (where, t)
