@@ -448,7 +448,46 @@ int life_dev_set_timing(life_dev *d, int on);
  * bytes_per_launch and the VALU count are booked as 0 -- the host does not
  * know how many tiles ran without a readback; life_dev_activity does. */
 #define LIFE_OPT_SKIP_DEAD 12
+/* LIFE_OPT_POPULATION (default 0; 1 on; any other value LIFE_EINVAL): while
+ * on, every life_dev_step(d, n) call records the live-cell count of the whole
+ * grid after each of its n generations, for life_dev_population to read.  The
+ * call stays asynchronous and nothing is read back during it; the state it
+ * computes is bit-identical with the option on or off.  A call may record at
+ * most 1048576 generations (LIFE_EINVAL with a message above that; split the
+ * call).  Device memory: 8 B per generation of the longest recorded call and
+ * shard, plus 16 KiB of counters per shard.
+ * Fast path -- the bit encoding, a temporal layout, every shard a multiple of
+ * 64 cells wide: the passes run census instances of the bit tiles (B3/S23 and
+ * table rule; whole-block, ring / interior, deep-halo, banded, half-height
+ * tail and skip-dead launches alike), which popcount the cells each tile owns
+ * after every generation of the pass inside its registers: no extra pass over
+ * HBM, still up to LIFE_OPT_BLOCK_GENS generations per launch.
+ * life_dev_last_path reports _TILES or _SKIP as without the option, a pass
+ * stays one timed launch, and life_dev_kernel_work counts the census's 2
+ * operations per pair row and generation.
+ * Every other device (the byte encoding, one-cell aprons, a shard width that
+ * is no multiple of 64) gets the same trace the plain way: one generation per
+ * launch, each followed by the census kernel of life_dev_live_count on the
+ * stream -- about the cost of a host loop of life_dev_step(d, 1) +
+ * life_dev_live_count(d) minus its readbacks and syncs.
+ * Precedence, as under a rule other than B3/S23: LIFE_OPT_FLOW,
+ * LIFE_OPT_SMALL_GRID and LIFE_OPT_PIPELINE are ignored while the option is on
+ * (those shapes run the per-launch tiles or the one-generation kernel, one
+ * launch per pass; the dataflow and small-grid kernels record nothing and
+ * pipelined passes overlap in time); LIFE_OPT_SKIP_DEAD keeps acting, and a
+ * pass of a recording call leaves the activity maps valid. */
+#define LIFE_OPT_POPULATION 13
 int life_dev_configure(life_dev *d, int option, int value);
+/* The population trace of the LAST life_dev_step call.  Blocking: waits for
+ * the device.  *generations (may be NULL) = the generations that call
+ * recorded: its n with LIFE_OPT_POPULATION on, 0 with the option off, for a
+ * call of 0 generations and before any call.  counts[g], g < min(max,
+ * *generations), = the live cells of the whole grid after generation g + 1 of
+ * that call, summed over all local shards; counts == NULL with max == 0 only
+ * queries the length.  In rank mode the sum across ranks is an all-reduce on
+ * the shard's communicator, as life_dev_live_count's, so the call is
+ * COLLECTIVE there (never executed with world > 1: one-GPU boxes). */
+int life_dev_population(life_dev *d, int64_t *counts, int64_t max, int64_t *generations);
 /* The skip-dead passes of the LAST life_dev_step call, summed: their number,
  * the tiles whose body ran, the tiles that only stored zeros over a block the
  * destination buffer held as possibly live, and the tiles of their tile

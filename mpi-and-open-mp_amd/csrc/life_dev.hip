@@ -140,6 +140,8 @@ void shard_free(Shard &s) {
     if (s.act_map[0]) (void)hipFree(s.act_map[0]);  // one allocation holds both maps
     if (s.act_cls) (void)hipFree(s.act_cls);
     if (s.act_cnt) (void)hipFree(s.act_cnt);
+    if (s.pop_cnt) (void)hipFree(s.pop_cnt);
+    if (s.pop_trace) (void)hipFree(s.pop_trace);
     if (s.d_count) (void)hipFree(s.d_count);
     if (s.h_count) (void)hipHostFree(s.h_count);
     for (hipEvent_t e : {s.ev_halo, s.ev_sync, s.ev_int, s.ev_entry, s.own_a, s.own_b})
@@ -546,6 +548,11 @@ int life_dev_configure(life_dev *d, int option, int value) {
         if (value < 0 || value > 1) return LIFE_EINVAL;
         if (value) d->act_valid = false;  // turning it on: the maps are rebuilt by the next step call
         d->skip_dead = value != 0;
+        return LIFE_OK;
+    case LIFE_OPT_POPULATION:
+        // accepted on every device: census tiles where life_step.hip pop_fast, else a census per generation
+        if (value < 0 || value > 1) return LIFE_EINVAL;
+        d->population = value != 0;
         return LIFE_OK;
     case LIFE_OPT_LOOPBACK: {
         // 1: both axes, 2: x only, 3: y only (the axes a real partition of

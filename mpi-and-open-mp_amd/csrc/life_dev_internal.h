@@ -105,6 +105,11 @@ struct Shard {
     uint8_t *act_cls = nullptr;
     size_t act_cls_cap = 0;
     unsigned long long *act_cnt = nullptr;
+    // population trace (LIFE_OPT_POPULATION; allocated by the first such call): pop_cnt the striped
+    // counters of the pass in flight (life_kernels.h kPopCounterBytes, zero between passes), pop_trace
+    // the last call's counts of this shard, one per generation (grows on demand)
+    unsigned long long *pop_cnt = nullptr, *pop_trace = nullptr;
+    size_t pop_cap = 0;
     std::vector<life_halo_op> plan;
     bool corners = false;  // the plan exchanges the four corner blocks itself (fused, one phase)
     // resolved with the plan (plan_halos): every op's staging slot; LOCAL
@@ -161,6 +166,10 @@ struct life_dev {
     // step call and the tiles of their grids (life_dev_activity)
     bool skip_dead = false, act_valid = false;
     int64_t act_passes = 0, act_total = 0;
+    // LIFE_OPT_POPULATION: the option; the generations the last step call recorded and those folded so
+    // far; whether the shard traces were already summed over the ranks (life_dev_population)
+    bool population = false, pop_reduced = false;
+    int64_t pop_n = 0, pop_pos = 0;
     life::rt::TimedLaunch *call_timer = nullptr;  // kTimeCall: the pair bracketing the current step call
     std::vector<life::rt::Shard> shards;
     double acc_ms = 0.0;

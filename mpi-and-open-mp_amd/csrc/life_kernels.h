@@ -133,7 +133,25 @@ struct Extend {
 hipError_t launch_tstep(const life_layout &L, const uint8_t *in, uint8_t *out, const TileRegion *r, int nreg,
                         int m, Wrap wrap, hipStream_t s,
                         double *valu_lane_ops = nullptr, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
-                        Extend ext = Extend{}, int64_t concurrent = 0, const RuleWords *rule = nullptr);
+                        Extend ext = Extend{}, int64_t concurrent = 0, const RuleWords *rule = nullptr,
+                        unsigned long long *pop = nullptr);
+// Census instances of the bit tiles (LIFE_OPT_POPULATION): with `pop` (here
+// and in launch_tskip; bit shards of whole pairs, w % 64 == 0) every tile of
+// the launch also adds the live cells it owns after each of the m generations
+// to pop[stripe * kPopGens + g], g < m, the stripe chosen by the workgroup
+// index -- kPopStripes stripes of kPopGens counters, 256 B each, so that the
+// tiles' atomics spread over as many cache lines (LIFE_POP_STRIPES, compile
+// time, A/B: profiles/population).  launch_pop_fold, stream-ordered behind
+// every launch of the pass, stores the m sums over the stripes to trace[0, m)
+// and leaves all counters zero; the counters start zeroed.
+constexpr int kPopGens = 32;  // generations per pass at most (launch_tstep: m <= 32)
+#ifndef LIFE_POP_STRIPES
+#define LIFE_POP_STRIPES 64
+#endif
+constexpr int kPopStripes = LIFE_POP_STRIPES;
+static_assert(kPopStripes >= 1 && (kPopStripes & (kPopStripes - 1)) == 0, "stripes: a power of two");
+constexpr size_t kPopCounterBytes = (size_t)kPopStripes * kPopGens * sizeof(unsigned long long);
+hipError_t launch_pop_fold(unsigned long long *cnt, unsigned long long *trace, int m, hipStream_t s);
 // One skip-dead pass (LIFE_OPT_SKIP_DEAD) of m generations over a single bit
 // shard whose axes both wrap in the stencil (w a multiple of 64), three
 // stream-ordered steps on `s`: the plan kernel classes every tile of the
@@ -146,7 +164,7 @@ int64_t skip_tiles(const life_layout &L, int m);  // tiles of such a pass (grows
 int64_t act_map_bytes(const life_layout &L);      // one buffer's activity map
 hipError_t launch_tskip(const life_layout &L, const uint8_t *in, uint8_t *out, int m, const uint32_t *src_map,
                         uint32_t *dst_map, uint8_t *cls, unsigned long long *cnt, hipStream_t s,
-                        const RuleWords *rule = nullptr);
+                        const RuleWords *rule = nullptr, unsigned long long *pop = nullptr);
 // Computes (and caches) the launch-tail plans launch_tstep will use for the
 // whole-shard launches of layout L at m = 1 .. mmax generations (with
 // ext_y: also every deep-halo extension 0 .. K - m), so that a step call
@@ -161,7 +179,11 @@ int tile_waves(bool bit);         // waves per tile workgroup: 8
 // VALU instructions the lanes at one lane position of a tile's waves issue
 // for m generations (the op-count model of life_kernels.hip tstep_kernel,
 // checked against the SQ_INSTS_VALU counter in profiles/); x 64 lanes x tiles.
-double tstep_valu_per_tile_lane(int m, bool byte, bool rule = false);
+double tstep_valu_per_tile_lane(int m, bool byte, bool rule = false, bool pop = false);
+// VALU instructions per pair row and generation the census instances add
+// (two v_bcnt_u32_b32, each adding to the lane's count);
+// life_mi355x.POP_VALU_PER_PAIR_ROW in the binding.
+constexpr int kPopValuPerPairRow = 2;
 // VALU instructions per pair row and generation of the table-rule tiles
 // (trule_bit_kernel): 2 v_alignbit + 4 (two full adders) + 2 x 25 (the tail);
 // B3/S23: 22.  life_mi355x.RULE_VALU_PER_PAIR_ROW in the binding.

@@ -409,8 +409,22 @@ struct TArgs {
     int32_t xext;
 };
 
+// Census instances of the bit tiles (LIFE_OPT_POPULATION): a
+// tile also counts, after every generation of its pass, the live cells it
+// owns -- the rows and lanes it will store, without the apron rows and pairs
+// a deep-halo pass advances -- and adds the pass's m counts to one stripe of
+// the shard's counters: cnt[stripe][kPopGens], the stripe chosen by the
+// workgroup index (kPopStripes, a power of two; each stripe on cache lines of
+// its own).  The launcher's fold kernel sums the stripes into the trace.
+// Whole pairs only: a shard whose width is no multiple of 64 holds apron cells
+// in its last pair and takes the generic path (life_step.hip).
+struct PopArgs {
+    unsigned long long *cnt;
+    int64_t y0, y1;  // the counted rows [y0, y1) of the launch's tile grid: the shard's real owned rows
+};
+
 template <int NW>
-using Xch = uint32_t[2][NW][4][64];  // byte tiles: [parity][wave][top s0/s1, bottom s0/s1][lane]
+using Xch =uint32_t[2][NW][4][64];  // byte tiles: [parity][wave][top s0/s1, bottom s0/s1][lane]
 // bit tiles: [parity][1 + wave][top e0 e1 o0 o1, bottom ...][lane]; slots 0
 // and NW + 1 stay zero (the dead rows beyond the window): no branch on the
 // wave index in the generation loop
@@ -483,11 +497,21 @@ struct XchB {
 // (life_act.h: R <= kActRows rows of a wave lie in at most two map rows, all in
 // map column tx).  Compiles to nothing when off: the other instances keep
 // their code.
-template <int R, bool WRAPX, bool WRAPY, int FLOW, int NW, bool BAND = false, class RP = ConwayRule, bool ACT = false>
+//
+// POP (tpop kernels, LIFE_OPT_POPULATION): after each generation's update a
+// wave popcounts the cells it owns (2 v_bcnt per pair row, kPopValuPerPairRow)
+// and leaves the wave's sum in pl[g][wave] (LDS); after the stores one wave
+// adds the m sums of the workgroup to its stripe of pa->cnt.  The ownership
+// test is recomputed from the lane id in every generation, as the store code
+// does after the loop: nothing more stays live across the loop.  Compiles to
+// nothing when off, as ACT.
+template <int R, bool WRAPX, bool WRAPY, int FLOW, int NW, bool BAND = false, class RP = ConwayRule, bool ACT = false,
+          bool POP = false>
 __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in, uint8_t *out, int64_t tx,
                                               int64_t ty, XchB<NW> &xb, int gsh = 6, int nb = 1,
                                               int64_t ybase = 0, int64_t yend = -1, int64_t org = 0, int own = 62,
-                                              const RP &rule = RP{}, uint32_t *act = nullptr) {
+                                              const RP &rule = RP{}, uint32_t *act = nullptr,
+                                              const PopArgs *pa = nullptr, uint32_t *pl = nullptr) {
     XchP<NW> &xch = xb.s;
     static_assert(R >= 3, "window");
     static_assert(!ACT || (!BAND && !FLOW && R <= kActRows), "activity map: plain tiles");
@@ -567,6 +591,17 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
     // beyond the window): a branch there split the loop body into blocks and
     // the every row's ds_bpermute was hoisted above it, their 2R results
     // spilling (46-83 VGPRs at R = 24).
+    // POP: bit r set when register row r of a lane whose rows start at owned row yb is counted -- one
+    // of the rows the wave stores (r0, r1 and ylim below) inside the counted rows [pa->y0, pa->y1)
+    auto pop_rows = [&](int64_t yb) -> uint32_t {
+        const int64_t R64 = R;
+        const int64_t yl = min(yend >= 0 ? yend : a.h, pa->y1);
+        const int lo = max(min(max(K - wi * R, 0), R), (int)min(max(pa->y0 - yb, (int64_t)0), R64));
+        const int hi = min(min(max(NW * R - K - wi * R, 0), R), (int)min(max(yl - yb, (int64_t)0), R64));
+        return hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
+    };
+    // a plain tile's mask is wave-uniform: one SGPR across the loop (banded lanes recompute theirs)
+    const uint32_t rm_s = POP && !BAND ? (uint32_t)__builtin_amdgcn_readfirstlane((int)pop_rows(y0)) : 0u;
     if (wi == 0 || wi == NW - 1)  // the dead slots (ordered by the first barrier below)
         for (int q = 0; q < 16; ++q) xch[q >> 3][wi == 0 ? 0 : NW + 1][q & 7][lane] = 0u;
     for (int g = 0; g < a.m; ++g) {
@@ -644,6 +679,29 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
             ve[R - 1] = rule(pe0, pe1, ce0, ce1, de0, de1, ve[R - 1]);
             vo[R - 1] = rule(po0, po1, co0, co1, do0, do1, vo[R - 1]);
         }
+        if (POP) {
+            // generation g + 1 of the pass: the cells this wave will store (st and the row tests
+            // below, without the xext apron pairs), inside the counted rows [pa->y0, pa->y1)
+            int l3 = (int)(threadIdx.x & 63);
+            asm volatile("" : "+v"(l3));
+            const int gl3 = BAND ? l3 >> gsh : 0;
+            const int pin3 = BAND ? l3 & ((1 << gsh) - 1) : l3;
+            const bool own3 = BAND ? (pin3 >= 1 && pin3 <= own && gl3 < nb)
+                                   : (l3 >= 1 && l3 <= 62 && tx * 62 + l3 - 1 < a.W);
+            // Straight-line code, no test per row: every row's two popcounts times its bit of the row
+            // mask (v_bcnt x 2 and a v_cndmask; the bit is scalar in a plain tile).  A branch here, even
+            // a wave-uniform one around the rows a wave does not own, split the loop body, the compiler
+            // hoisted the permutes above it and spilled 100-150 VGPRs.
+            const uint32_t rm = BAND ? pop_rows(y0 + (int64_t)(gl3 < nb ? gl3 : 0) * T) : rm_s;
+            uint32_t c = 0u;
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                c = __umul24((uint32_t)__popc(ve[r]) + (uint32_t)__popc(vo[r]), (rm >> r) & 1u) + c;
+            if (!own3) c = 0u;
+#pragma unroll
+            for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s);  // < 2^17: 64 lanes x R rows x 64 cells
+            if (l3 == 0) pl[g * NW + wi] = c;
+        }
     }
     // window rows [K, NW*R - K) are the tile's owned rows [ty*T, ty*T + T);
     // this wave's share of them (a half-height tile's ghost rows may span more
@@ -700,6 +758,18 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
 #pragma unroll
             for (int w = 0; w < kActWords; ++w)
                 if (am[k][w]) atomicOr(act + act_word(ar0 + k, tx, ncol, w), am[k][w]);
+    }
+    if (POP) {
+        // one wave, a lane per generation: the workgroup's counts into its stripe (a dead tile adds nothing)
+        __syncthreads();
+        if (wi == 0 && lane2 < a.m) {
+            uint32_t c = 0u;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) c += pl[lane2 * NW + w];
+            if (c)
+                atomicAdd(pa->cnt + (int64_t)(blockIdx.x & (kPopStripes - 1)) * kPopGens + lane2,
+                          (unsigned long long)c);
+        }
     }
 }
 
@@ -873,9 +943,10 @@ constexpr int bit_wpe(int NW, int R) { return NW == 16 ? (R <= 16 ? 8 : 4) : (R 
 // Banded item i of a region's last tile column: tile rows [ty0, ty0 + rows)
 // as the items of sub-column 0 (ceil(rows / B_0), B_i = 64 >> bgsh[i] tile
 // rows each), then those of sub-column 1.  Wave-uniform throughout.
-template <int RS, bool WRAPX, bool WRAPY, int NW, class RP = ConwayRule>
+template <int RS, bool WRAPX, bool WRAPY, int NW, class RP = ConwayRule, bool POP = false>
 __device__ __forceinline__ void band_item(const TArgs &a, int64_t i, int64_t ty0, int64_t rows, XchB<NW> &xch,
-                                          int64_t ybase = 0, int64_t yend = -1, const RP &rule = RP{}) {
+                                          int64_t ybase = 0, int64_t yend = -1, const RP &rule = RP{},
+                                          const PopArgs *pa = nullptr, uint32_t *pl = nullptr) {
     const int64_t n0 = (rows + (64 >> a.bgsh[0]) - 1) >> (6 - a.bgsh[0]);
     const bool second = a.nband > 1 && i >= n0;
     if (second) i -= n0;
@@ -883,8 +954,12 @@ __device__ __forceinline__ void band_item(const TArgs &a, int64_t i, int64_t ty0
     const int64_t org = second ? a.borg[1] : a.borg[0];
     const int64_t B = 64 >> gsh, t = i * B;  // first tile row of the item within the region
     const int nb = (int)(rows - t < B ? rows - t : B);
-    tile_body_bit<RS, WRAPX, WRAPY, 0, NW, true>(a, a.in, a.out, 0, ty0 + t, xch, gsh, nb, ybase, yend, org, own,
-                                                 rule);
+    if (POP)
+        tile_body_bit<RS, WRAPX, WRAPY, 0, NW, true, RP, false, POP>(a, a.in, a.out, 0, ty0 + t, xch, gsh, nb, ybase,
+                                                                     yend, org, own, rule, nullptr, pa, pl);
+    else
+        tile_body_bit<RS, WRAPX, WRAPY, 0, NW, true>(a, a.in, a.out, 0, ty0 + t, xch, gsh, nb, ybase, yend, org, own,
+                                                     rule);
 }
 
 // Item i of the tail (TArgs::tail_*): RS rows per wave, tile rows of TS =
@@ -894,12 +969,22 @@ __device__ __forceinline__ void band_item(const TArgs &a, int64_t i, int64_t ty0
 // tiles per row without it.  (Round 5's half tiles spanned
 // the last column as full-width tiles; banded they take (64 - o - 2) / 64
 // fewer lanes there.)
-template <int RS, bool WRAPX, bool WRAPY, int NW, class RP = ConwayRule>
-__device__ __forceinline__ void tail_item(const TArgs &a, int64_t i, XchB<NW> &xch, const RP &rule = RP{}) {
+template <int RS, bool WRAPX, bool WRAPY, int NW, class RP = ConwayRule, bool POP = false>
+__device__ __forceinline__ void tail_item(const TArgs &a, int64_t i, XchB<NW> &xch, const RP &rule = RP{},
+                                          const PopArgs *pa = nullptr, uint32_t *pl = nullptr) {
     const int64_t TS = (int64_t)NW * RS - 2 * a.m, y0 = a.tail_y, yend = a.tail_yend;
     const int64_t rows = (yend - y0 + TS - 1) / TS;
     const bool band = a.nband > 0 && a.tail_tx0 + a.tail_ntx == a.btx1;
     const int64_t ntxs = a.tail_ntx - (band ? 1 : 0), nfull = ntxs * rows;
+    if (POP) {
+        if (i < nfull)
+            tile_body_bit<RS, WRAPX, WRAPY, 0, NW, false, RP, false, POP>(a, a.in, a.out, a.tail_tx0 + i % ntxs,
+                                                                          i / ntxs, xch, 6, 1, y0, yend, 0, 62, rule,
+                                                                          nullptr, pa, pl);
+        else
+            band_item<RS, WRAPX, WRAPY, NW, RP, POP>(a, i - nfull, 0, rows, xch, y0, yend, rule, pa, pl);
+        return;
+    }
     if (i < nfull)
         tile_body_bit<RS, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, a.tail_tx0 + i % ntxs, i / ntxs, xch, 6, 1, y0, yend,
                                               0, 62, rule);
@@ -947,8 +1032,9 @@ __global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tstep_bit_kernel(TArg
 // tstep_bit_kernel's item dispatch again, under a rule policy, for the
 // table-rule kernel below (a twin for the reason given at step_body: the
 // B3/S23 instances keep their own text and so their code).
-template <int R, bool WRAPX, bool WRAPY, int NW, class RP>
-__device__ __forceinline__ void tstep_bit_body(const TArgs &a, XchB<NW> &xch, const RP &rule) {
+template <int R, bool WRAPX, bool WRAPY, int NW, class RP, bool POP = false>
+__device__ __forceinline__ void tstep_bit_body(const TArgs &a, XchB<NW> &xch, const RP &rule,
+                                               const PopArgs *pa = nullptr, uint32_t *pl = nullptr) {
     wg_trace(0);
     int64_t wg = blockIdx.x;
     if (wg < a.xcd_n) {  // per-XCD row-major runs, as tstep_bit_kernel
@@ -956,7 +1042,7 @@ __device__ __forceinline__ void tstep_bit_body(const TArgs &a, XchB<NW> &xch, co
         wg = (x < rem ? x * (per + 1) : rem * (per + 1) + (x - rem) * per) + k;
     }
     if (a.tail_ntx > 0 && wg >= a.tail_first) {
-        tail_item<R / 2, WRAPX, WRAPY, NW>(a, wg - a.tail_first, xch, rule);
+        tail_item<R / 2, WRAPX, WRAPY, NW, RP, POP>(a, wg - a.tail_first, xch, rule, pa, pl);
         wg_trace(1);
         return;
     }
@@ -970,9 +1056,14 @@ __device__ __forceinline__ void tstep_bit_body(const TArgs &a, XchB<NW> &xch, co
     const int64_t nfull = ntx * (a.ty1[k] - a.ty0[k]);
     if (wr < nfull) {
         const int64_t tx = a.tx0[k] + wr % ntx, ty = a.ty0[k] + wr / ntx;
-        tile_body_bit<R, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, tx, ty, xch, 6, 1, 0, -1, 0, 62, rule);
+        if (POP)
+            tile_body_bit<R, WRAPX, WRAPY, 0, NW, false, RP, false, POP>(a, a.in, a.out, tx, ty, xch, 6, 1, 0, -1, 0,
+                                                                         62, rule, nullptr, pa, pl);
+        else
+            tile_body_bit<R, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, tx, ty, xch, 6, 1, 0, -1, 0, 62, rule);
     } else {
-        band_item<R, WRAPX, WRAPY, NW>(a, wr - nfull, a.ty0[k], a.ty1[k] - a.ty0[k], xch, 0, -1, rule);
+        band_item<R, WRAPX, WRAPY, NW, RP, POP>(a, wr - nfull, a.ty0[k], a.ty1[k] - a.ty0[k], xch, 0, -1, rule, pa,
+                                                pl);
     }
     wg_trace(1);
 }
@@ -992,10 +1083,40 @@ struct RTArgs {
     TArgs t;
     RuleWords w;
 };
+// Waves per SIMD the B3/S23 census instances are compiled for (LIFE_POP_WPE,
+// compile time, A/B): 6 = 3 tiles per CU at <= 80 VGPRs, as the plain tiles
+// (the launch-tail plans count the same slots), 4 = 2 tiles at <= 128.
+#ifndef LIFE_POP_WPE
+#define LIFE_POP_WPE 6
+#endif
 template <int R, bool WRAPX, bool WRAPY, int NW>
 __global__ __launch_bounds__(64 * NW, LIFE_RULE_WPE) void trule_bit_kernel(RTArgs a) {
     __shared__ XchB<NW> xch;
     tstep_bit_body<R, WRAPX, WRAPY, NW>(a.t, xch, TableRule(a.w));
+}
+
+// The census instances of both (PopArgs): the same items through the same
+// dispatch, each tile also counting what it owns after every generation.
+struct PTArgs {
+    TArgs t;
+    PopArgs p;
+};
+template <int R, bool WRAPX, bool WRAPY, int NW>
+__global__ __launch_bounds__(64 * NW, LIFE_POP_WPE) void tpop_bit_kernel(PTArgs a) {
+    __shared__ XchB<NW> xch;
+    __shared__ uint32_t pl[kPopGens * NW];
+    tstep_bit_body<R, WRAPX, WRAPY, NW, ConwayRule, true>(a.t, xch, ConwayRule{}, &a.p, pl);
+}
+struct RPTArgs {
+    TArgs t;
+    RuleWords w;
+    PopArgs p;
+};
+template <int R, bool WRAPX, bool WRAPY, int NW>
+__global__ __launch_bounds__(64 * NW, LIFE_RULE_WPE) void tpop_rule_kernel(RPTArgs a) {
+    __shared__ XchB<NW> xch;
+    __shared__ uint32_t pl[kPopGens * NW];
+    tstep_bit_body<R, WRAPX, WRAPY, NW, TableRule, true>(a.t, xch, TableRule(a.w), &a.p, pl);
 }
 
 // ---- skip-dead passes (LIFE_OPT_SKIP_DEAD; DESIGN.md 5.9, life_act.h)
@@ -1048,8 +1169,9 @@ struct KArgs {
     uint32_t *act;       // the output buffer's map, zeroed
     int64_t ntx, nty;
 };
-template <int R, int NW, class RP>
-__device__ __forceinline__ void tskip_body(const KArgs &k, XchB<NW> &xch, const RP &rule) {
+template <int R, int NW, class RP, bool POP = false>
+__device__ __forceinline__ void tskip_body(const KArgs &k, XchB<NW> &xch, const RP &rule,
+                                           const PopArgs *pa = nullptr, uint32_t *pl = nullptr) {
     const TArgs &a = k.t;
     const int64_t wg = blockIdx.x;
     if (wg >= k.ntx * k.nty) return;
@@ -1066,7 +1188,12 @@ __device__ __forceinline__ void tskip_body(const KArgs &k, XchB<NW> &xch, const 
                 *reinterpret_cast<uint64_t *>(a.out + (a.ya + y) * a.pitch + a.xoff + 8 * j) = 0ull;
         return;
     }
-    tile_body_bit<R, true, true, 0, NW, false, RP, true>(a, a.in, a.out, tx, ty, xch, 6, 1, 0, -1, 0, 62, rule, k.act);
+    if (POP)
+        tile_body_bit<R, true, true, 0, NW, false, RP, true, POP>(a, a.in, a.out, tx, ty, xch, 6, 1, 0, -1, 0, 62,
+                                                                  rule, k.act, pa, pl);
+    else
+        tile_body_bit<R, true, true, 0, NW, false, RP, true>(a, a.in, a.out, tx, ty, xch, 6, 1, 0, -1, 0, 62, rule,
+                                                             k.act);
 }
 template <int R, int NW>
 __global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tskip_bit_kernel(KArgs k) {
@@ -1081,6 +1208,42 @@ template <int R, int NW>
 __global__ __launch_bounds__(64 * NW, LIFE_RULE_WPE) void tskip_rule_kernel(RKArgs a) {
     __shared__ XchB<NW> xch;
     tskip_body<R, NW>(a.k, xch, TableRule(a.w));
+}
+// their census instances
+struct PKArgs {
+    KArgs k;
+    PopArgs p;
+};
+template <int R, int NW>
+__global__ __launch_bounds__(64 * NW, LIFE_POP_WPE) void tpop_skip_kernel(PKArgs a) {
+    __shared__ XchB<NW> xch;
+    __shared__ uint32_t pl[kPopGens * NW];
+    tskip_body<R, NW, ConwayRule, true>(a.k, xch, ConwayRule{}, &a.p, pl);
+}
+struct RPKArgs {
+    KArgs k;
+    RuleWords w;
+    PopArgs p;
+};
+template <int R, int NW>
+__global__ __launch_bounds__(64 * NW, LIFE_RULE_WPE) void tpop_skip_rule_kernel(RPKArgs a) {
+    __shared__ XchB<NW> xch;
+    __shared__ uint32_t pl[kPopGens * NW];
+    tskip_body<R, NW, TableRule, true>(a.k, xch, TableRule(a.w), &a.p, pl);
+}
+
+// Folds the stripes of a pass into the trace and zeroes them: block g < m
+// stores the sum of generation g's counters to trace[g]; every block (the
+// launch has kPopGens) leaves its counters zero for the next pass.
+__global__ __launch_bounds__(64) void pop_fold_kernel(unsigned long long *cnt, unsigned long long *trace, int m) {
+    const int g = blockIdx.x;
+    unsigned long long c = 0;
+    for (int s = threadIdx.x; s < kPopStripes; s += 64) {
+        c += cnt[(int64_t)s * kPopGens + g];
+        cnt[(int64_t)s * kPopGens + g] = 0ull;
+    }
+    for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s);
+    if (threadIdx.x == 0 && g < m) trace[g] = c;
 }
 
 template <int R, int GK, bool WRAPX, bool WRAPY, int NW>
@@ -1593,10 +1756,13 @@ int tile_waves(bool) { return kStackWaves; }
 // rule for both dwords (16 v_bitop3) = 22 (+ 2 ds_bpermute on the LDS pipe);
 // byte, per word row: the drifting frame (12) plus pack (8 v_dot4 + 3
 // shifts) and unpack (8 x bfe/mul24/and) once per row and launch.
-double tstep_valu_per_tile_lane(int m, bool byte, bool rule) {
+// Census instances (pop): kPopValuPerPairRow more per pair row and generation
+// (the two v_bcnt; the wave's reduction and the ownership test are per
+// generation, not per row, and not modelled).
+double tstep_valu_per_tile_lane(int m, bool byte, bool rule, bool pop) {
     if (byte) return (double)kStackWaves * (double)temporal_rows(false) * (12.0 * (double)m + 35.0);
-    return (double)tile_waves(true) * (double)temporal_rows(true) * (rule ? (double)kRuleValuPerPairRow : 22.0) *
-           (double)m;
+    return (double)tile_waves(true) * (double)temporal_rows(true) *
+           ((rule ? (double)kRuleValuPerPairRow : 22.0) + (pop ? (double)kPopValuPerPairRow : 0.0)) * (double)m;
 }
 
 void set_temporal_rows(int kernel, int nr) {
@@ -1751,6 +1917,29 @@ const void *rule_k(Wrap wrap) {
     const int R = temporal_rows(true), NW = tile_waves(true);
 #define LIFE_BIT_CASE(r, nw) \
     if (R == r && NW == nw) return rule_fn<r, nw>(wrap);
+    LIFE_BIT_SHAPES(LIFE_BIT_CASE)
+#undef LIFE_BIT_CASE
+    return nullptr;
+}
+
+// the census instances of both (tpop_bit_kernel / tpop_rule_kernel)
+template <int R, int NW>
+const void *pop_fn(Wrap wrap, bool rule) {
+    if (rule) {
+        if (wrap.x && wrap.y) return (const void *)tpop_rule_kernel<R, true, true, NW>;
+        if (wrap.x) return (const void *)tpop_rule_kernel<R, true, false, NW>;
+        if (wrap.y) return (const void *)tpop_rule_kernel<R, false, true, NW>;
+        return (const void *)tpop_rule_kernel<R, false, false, NW>;
+    }
+    if (wrap.x && wrap.y) return (const void *)tpop_bit_kernel<R, true, true, NW>;
+    if (wrap.x) return (const void *)tpop_bit_kernel<R, true, false, NW>;
+    if (wrap.y) return (const void *)tpop_bit_kernel<R, false, true, NW>;
+    return (const void *)tpop_bit_kernel<R, false, false, NW>;
+}
+const void *pop_k(Wrap wrap, bool rule) {
+    const int R = temporal_rows(true), NW = tile_waves(true);
+#define LIFE_BIT_CASE(r, nw) \
+    if (R == r && NW == nw) return pop_fn<r, nw>(wrap, rule);
     LIFE_BIT_SHAPES(LIFE_BIT_CASE)
 #undef LIFE_BIT_CASE
     return nullptr;
@@ -1923,10 +2112,11 @@ static void set_bands(TArgs &a, const TileGeom &g) {
 
 hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out, const TileRegion *r, int nreg,
                         int m, Wrap wrap, hipStream_t s, double *valu_lane_ops, hipEvent_t ev0, hipEvent_t ev1,
-                        Extend ext, int64_t concurrent, const RuleWords *rule) {
+                        Extend ext, int64_t concurrent, const RuleWords *rule, unsigned long long *pop) {
     const int K = Lin.generations_per_exchange;
     const bool bit = is_bit(Lin);
     if (rule && !bit) return hipErrorInvalidValue;  // no quiet B3/S23 in its place
+    if (pop && (!bit || Lin.w % 64 != 0 || m > kPopGens)) return hipErrorInvalidValue;  // whole pairs (PopArgs)
     // m <= 32: the tile's edge lanes absorb at most 32 wrong cells; m <= the
     // apron depth a partitioned axis provides.  Deep-halo passes: bit only
     // (the byte windows hold K ghost rows whatever m is), the window's top
@@ -1993,10 +2183,22 @@ hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out,
     const bool split = a.tail_ntx > 0;
     a.xcd_n = (bit ? xcd_order_enabled() : xcd_order_byte_enabled()) ? (split ? a.tail_first : items) : 0;
     if (valu_lane_ops) {
-        const double lane = 64.0 * tstep_valu_per_tile_lane(m, !bit, rule != nullptr);
+        const double lane = 64.0 * tstep_valu_per_tile_lane(m, !bit, rule != nullptr, pop != nullptr);
         *valu_lane_ops = (double)(split ? a.tail_first : items) * lane;
         if (split)  // half tiles: R / 2 register rows per wave
             *valu_lane_ops += (double)(items - a.tail_first) * lane * 0.5;
+    }
+    if (pop) {
+        // the counted rows: the shard's own, not the apron rows a deep-halo pass advances
+        const PopArgs pa{pop, ext.y, ext.y + Lin.h};
+        const void *pfn = pop_k(wrap, rule != nullptr);
+        if (!pfn) return hipErrorInvalidValue;
+        if (rule) {
+            RPTArgs ra{a, *rule, pa};
+            return launch_fn(pfn, (unsigned)items, 64u * (unsigned)tile_waves(true), &ra, s, ev0, ev1);
+        }
+        PTArgs ta{a, pa};
+        return launch_fn(pfn, (unsigned)items, 64u * (unsigned)tile_waves(true), &ta, s, ev0, ev1);
     }
     if (rule) {
         const void *rfn = rule_k(wrap);
@@ -2021,7 +2223,22 @@ const void *skip_k(bool rule) {
 #undef LIFE_BIT_CASE
     return nullptr;
 }
+const void *skip_pop_k(bool rule) {
+    const int R = temporal_rows(true), NW = tile_waves(true);
+#define LIFE_BIT_CASE(r, nw)  \
+    if (R == r && NW == nw) \
+        return rule ? (const void *)tpop_skip_rule_kernel<r, nw> : (const void *)tpop_skip_kernel<r, nw>;
+    LIFE_BIT_SHAPES(LIFE_BIT_CASE)
+#undef LIFE_BIT_CASE
+    return nullptr;
+}
 }  // namespace
+
+hipError_t launch_pop_fold(unsigned long long *cnt, unsigned long long *trace, int m, hipStream_t s) {
+    if (m < 0 || m > kPopGens) return hipErrorInvalidValue;
+    pop_fold_kernel<<<kPopGens, 64, 0, s>>>(cnt, trace, m);
+    return hipGetLastError();
+}
 
 int64_t act_map_bytes(const life_layout &L) {
     return act_cols((L.w + 63) / 64) * act_rows(L.h) * kActWords * (int64_t)sizeof(uint32_t);
@@ -2035,7 +2252,7 @@ int64_t skip_tiles(const life_layout &L, int m) {
 
 hipError_t launch_tskip(const life_layout &L, const uint8_t *in, uint8_t *out, int m, const uint32_t *src_map,
                         uint32_t *dst_map, uint8_t *cls, unsigned long long *cnt, hipStream_t s,
-                        const RuleWords *rule) {
+                        const RuleWords *rule, unsigned long long *pop) {
     const int K = L.generations_per_exchange;
     const int64_t T = (int64_t)tile_waves(true) * temporal_rows(true) - 2 * (int64_t)m;
     // both axes wrap in the stencil: whole pairs, no apron to fill
@@ -2064,6 +2281,18 @@ hipError_t launch_tskip(const life_layout &L, const uint8_t *in, uint8_t *out, i
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(dst_map, 0, (size_t)act_map_bytes(L), s);
     if (e != hipSuccess) return e;
+    if (pop) {
+        if (m > kPopGens) return hipErrorInvalidValue;
+        const PopArgs pa{pop, 0, L.h};
+        const void *pfn = skip_pop_k(rule != nullptr);
+        if (!pfn) return hipErrorInvalidValue;
+        if (rule) {
+            RPKArgs ra{k, *rule, pa};
+            return launch_fn(pfn, (unsigned)tiles, 64u * (unsigned)tile_waves(true), &ra, s, nullptr, nullptr);
+        }
+        PKArgs ka{k, pa};
+        return launch_fn(pfn, (unsigned)tiles, 64u * (unsigned)tile_waves(true), &ka, s, nullptr, nullptr);
+    }
     const void *fn = skip_k(rule != nullptr);
     if (!fn) return hipErrorInvalidValue;
     if (rule) {

@@ -21,7 +21,64 @@ constexpr double kFlowAutoRounds = 5.0;
 // fewest passes a call runs in the dataflow form
 constexpr int64_t kFlowMinPasses = 4;
 
+// LIFE_OPT_POPULATION: generations one step call may record (8 B each per shard)
+constexpr int64_t kPopMaxGens = 1 << 20;
+
 namespace {
+
+// ---- population trace (LIFE_OPT_POPULATION)
+// The census instances of the bit tiles take every pass of the call (fast
+// path): the bit encoding, a temporal layout, every shard whole pairs wide (a
+// narrower last pair holds apron cells, which a popcount would take for the
+// shard's own).  Every other device steps one generation per launch and runs
+// the census kernel behind it (step_census).
+bool pop_fast(const life_dev *d) {
+    if (!d->population || d->kernel != LIFE_KERNEL_BIT || !temporal(d)) return false;
+    for (const Shard &s : d->shards)
+        if (s.lay.w % 64 != 0) return false;
+    return true;
+}
+// the counters the tile launches of shard s add to (null: the plain instances)
+unsigned long long *pop_of(const life_dev *d, const Shard &s) { return pop_fast(d) ? s.pop_cnt : nullptr; }
+
+// The start of a recording call: the shards' counters (zeroed, on the compute
+// stream) and room for `generations` counts.
+int pop_begin(life_dev *d, int64_t generations) {
+    d->pop_n = d->pop_pos = 0;
+    d->pop_reduced = false;
+    if (!d->population) return LIFE_OK;
+    if (generations > kPopMaxGens) {
+        set_err("LIFE_OPT_POPULATION: a step call records at most %lld generations (%lld asked)",
+                (long long)kPopMaxGens, (long long)generations);
+        return LIFE_EINVAL;
+    }
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        if (!s.pop_cnt) HIPCHK(hipMalloc(&s.pop_cnt, life::kPopCounterBytes));
+        if ((size_t)generations > s.pop_cap) {
+            if (s.pop_trace) HIPCHK(hipFree(s.pop_trace));  // (waits for the device)
+            s.pop_trace = nullptr;
+            s.pop_cap = 0;
+            HIPCHK(hipMalloc(&s.pop_trace, (size_t)generations * sizeof(unsigned long long)));
+            s.pop_cap = (size_t)generations;
+        }
+        HIPCHK(hipMemsetAsync(s.pop_cnt, 0, life::kPopCounterBytes, s.stream));
+    }
+    d->pop_n = generations;
+    return LIFE_OK;
+}
+
+// Behind a pass of m generations (every stream of it joined into the compute
+// stream): the counters folded into the next m entries of each shard's trace.
+int pop_fold(life_dev *d, int m) {
+    if (d->pop_n == 0) return LIFE_OK;
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        HIPCHK(life::launch_pop_fold(s.pop_cnt, s.pop_trace + d->pop_pos, m, s.stream));
+    }
+    d->pop_pos += m;
+    return LIFE_OK;
+}
 
 // Launches one stencil region on `st`; when timing is on and `timed`,
 // brackets it with HIP events on that stream and books its algorithmic bytes
@@ -51,7 +108,7 @@ int launch_tiles(life_dev *d, Shard &s, const life::TileRegion *r, int nreg, int
     CHK(bracket_begin(d, s, timed, 1, kExtModeExt | kExtModeCall, false, st, &b));
     double valu = 0.0;
     HIPCHK(life::launch_tstep(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], r, nreg, m, wrap_of(d), st, &valu, b.ext_a,
-                              b.ext_b, xt, concurrent, rule_of(d)));
+                              b.ext_b, xt, concurrent, rule_of(d), pop_of(d, s)));
     CHK(bracket_end(b, st));
     if (b.t) {  // (no timer counts it -- span-only timing, LIFE_TIMING_MODE=3: no booking)
         const life::TileGeom g = life::tile_geom(life::extended_layout(s.lay, xt), m);
@@ -423,7 +480,9 @@ life::RegWinPlan win_plan(const life_dev *d) {
 }
 
 bool small_grid(const life_dev *d) {
-    // (the resident kernels are B3/S23 only: under another rule the streaming kernels run)
+    // (the resident kernels are B3/S23 only: under another rule the streaming kernels run; they record
+    // no population either)
+    if (d->population) return false;
     if (d->world != 1 || d->shards.size() != 1 || d->small_mode == 0 || d->loop != 0 || d->table) return false;
     const life_layout &L = d->shards[0].lay;
     if (win_plan(d).blocks > 0) return true;
@@ -471,7 +530,7 @@ int step_small(life_dev *d, int64_t generations) {
 // generations in (1 / 2, the hand-off forms), or 0 (per-launch tiles; always
 // under a rule other than B3/S23: the dataflow tiles have no such instance).
 int flow_form(const life_dev *d, int *m_out) {
-    if (!d->flow || d->table || d->shards.size() != 1 || d->world != 1 || part(d, 0) || part(d, 1) || self_wrap_x(d) ||
+    if (!d->flow || d->table || d->population || d->shards.size() != 1 || d->world != 1 || part(d, 0) || part(d, 1) || self_wrap_x(d) ||
         d->kernel != LIFE_KERNEL_BIT)
         return 0;
     const life_layout &L = d->shards[0].lay;
@@ -633,8 +692,9 @@ int step_skip(life_dev *d, int64_t generations) {
         Bracket b;
         CHK(bracket_begin(d, s, true, 1, kExtNever, false, s.stream, &b));
         HIPCHK(life::launch_tskip(L, s.buf[s.cur], s.buf[s.cur ^ 1], p.m, s.act_map[s.cur], s.act_map[s.cur ^ 1],
-                                  s.act_cls, s.act_cnt, s.stream, rule_of(d)));
+                                  s.act_cls, s.act_cnt, s.stream, rule_of(d), pop_of(d, s)));
         CHK(bracket_end(b, s.stream));
+        CHK(pop_fold(d, p.m));  // (outside the bracket: the pass stays one timed launch)
         if (b.t) book(d, true, (double)L.w * (double)L.h, (double)p.m, 0.0, 0.0);
         s.cur ^= 1;
         d->act_passes++;
@@ -645,10 +705,36 @@ int step_skip(life_dev *d, int64_t generations) {
     return LIFE_OK;
 }
 
+// A recording call of a device the census tiles do not take (pop_fast): one
+// generation per launch, the census kernel behind each on the compute stream
+// (count and checksum land in the first two counters; the fold stores the
+// count and zeroes both).  Nothing is read back.
+int step_census(life_dev *d, int64_t generations) {
+    const bool tiles = temporal(d);
+    d->last_path = tiles ? LIFE_PATH_TILES : LIFE_PATH_ONEGEN;
+    const int K = d->shards[0].lay.generations_per_exchange;
+    for (int64_t g = 0; g < generations; g++) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (tiles)
+            CHK(generation_block(d, life::next_pass(K, max_pass_gens(d), deep_halo(d), d->since, 1)));
+        else
+            CHK(generation(d));
+        for (Shard &s : d->shards) {
+            HIPCHK(hipSetDevice(s.device));
+            HIPCHK(life::launch_census(s.lay, d->nx, s.buf[s.cur], s.pop_cnt, s.stream));
+        }
+        CHK(pop_fold(d, 1));
+        note_pass(d, t0);
+    }
+    return LIFE_OK;
+}
+
 // The launches of one step call (life_dev_step after its entry fence).
 int step_body(life_dev *d, int64_t generations) {
+    CHK(pop_begin(d, generations));
     if (skip_dead_applies(d)) return step_skip(d, generations);
     d->act_valid = false;  // a pass of any other form leaves the activity maps behind
+    if (d->population && !pop_fast(d)) return step_census(d, generations);
     if (small_grid(d)) {
         d->last_path = LIFE_PATH_SMALL;
         constexpr int64_t kChunk = 1 << 20;  // generations per resident launch
@@ -667,6 +753,7 @@ int step_body(life_dev *d, int64_t generations) {
             const life::PassPlan p = life::next_pass(K, max_pass_gens(d), deep_halo(d), d->since, generations - g);
             const auto t0 = std::chrono::steady_clock::now();
             CHK(generation_block(d, p));
+            CHK(pop_fold(d, p.m));
             note_pass(d, t0);
             g += p.m;
         }
@@ -689,7 +776,9 @@ int step_body(life_dev *d, int64_t generations) {
 // one pair, span-only timing and no timing pipeline); fewer than 2 passes
 // behind the dataflow form's share; no plan for the first pass's tile grid.
 int pipe_regions(const life_dev *d, int64_t generations) {
-    if (d->pipe == 0 || d->shards.size() != 1 || d->world != 1 || part(d, 0) || part(d, 1) || self_wrap_x(d) ||
+    // (a recording call runs one launch per pass: pipelined passes overlap in time and would need a
+    // counter set per pass in flight)
+    if (d->pipe == 0 || d->population || d->shards.size() != 1 || d->world != 1 || part(d, 0) || part(d, 1) || self_wrap_x(d) ||
         !temporal(d) || small_grid(d) || skip_dead_applies(d))  // (skip-dead passes run whole, on one stream)
         return 0;
     if (d->timing && d->launch_events && timing_mode() != kTimeCall && timing_mode() != kTimeOff) return 0;
@@ -814,7 +903,10 @@ extern "C" {
 
 int life_dev_step(life_dev *d, int64_t generations) {
     if (!d || generations < 0) return LIFE_EINVAL;
-    if (generations == 0) return LIFE_OK;
+    if (generations == 0) {
+        d->pop_n = d->pop_pos = 0;  // the last call recorded nothing
+        return LIFE_OK;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     d->call_passes = 0;
     d->call_pass_max_ms = 0.0;
@@ -826,6 +918,31 @@ int life_dev_step(life_dev *d, int64_t generations) {
 }
 
 int life_dev_last_path(life_dev *d) { return d ? d->last_path : LIFE_EINVAL; }
+
+int life_dev_population(life_dev *d, int64_t *counts, int64_t max, int64_t *generations) {
+    if (!d || max < 0 || (!counts && max > 0)) return LIFE_EINVAL;
+    CHK(life_dev_sync(d));
+    // a call that failed half way recorded pop_pos < pop_n generations
+    const int64_t n = std::min(d->pop_n, d->pop_pos);
+    if (generations) *generations = n;
+    const int64_t take = std::min(n, max);
+    if (take <= 0) return LIFE_OK;
+    std::vector<unsigned long long> h((size_t)take);
+    std::fill(counts, counts + take, (int64_t)0);
+    for (Shard &s : d->shards) {
+        HIPCHK(hipSetDevice(s.device));
+        // rank mode: every rank's shard summed into every rank's trace, once (the census's all-reduce;
+        // never executed with world > 1: one-GPU boxes)
+        if (d->rank_mode && s.comm && !d->pop_reduced)
+            NCCLCHK(ncclAllReduce(s.pop_trace, s.pop_trace, (size_t)n, ncclUint64, ncclSum, s.comm, s.stream));
+        HIPCHK(hipMemcpyAsync(h.data(), s.pop_trace, (size_t)take * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              s.stream));
+        CHK(bounded_sync(s, "population all-reduce", -1));
+        for (int64_t g = 0; g < take; g++) counts[g] += (int64_t)h[(size_t)g];
+    }
+    d->pop_reduced = true;
+    return LIFE_OK;
+}
 
 int life_dev_activity(life_dev *d, int64_t *passes, int64_t *tiles_run, int64_t *tiles_cleared, int64_t *tiles_total) {
     if (!d) return LIFE_EINVAL;

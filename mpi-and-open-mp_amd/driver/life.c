@@ -47,6 +47,13 @@
  *   --rule TEXT       the Life-like rule, "B36/S23" or Golly's "23/36" (S/B)
  *                     (life_rule_parse, life_dev_set_rule; default B3/S23, the
  *                     reference's rule; bit kernel only, no B0 rules)
+ *   --population FILE write the population curve: one line "generation live"
+ *                     ("%lld %lld\n") for the starting generation (a
+ *                     life_dev_live_count before the first step) and for every
+ *                     generation of the run (LIFE_OPT_POPULATION: counted inside
+ *                     the stepping kernels, read with life_dev_population after
+ *                     each step call, between frames); frames and the printed
+ *                     time keep their format
  *   --live            print the live-cell count after the run to stderr
  *   --rank-mode       one-process-per-GPU mode even without a launcher (world 1)
  *
@@ -350,7 +357,7 @@ static uint8_t *unpack_bits(const uint8_t *packed, int64_t w, int64_t h) {
 }
 
 int main(int argc, char **argv) {
-    const char *cfg_path = NULL, *resume = NULL;
+    const char *cfg_path = NULL, *resume = NULL, *pop_path = NULL;
     int gpus = 1, kernel = LIFE_KERNEL_BIT, vtk = 1, live = 0, have_random = 0, bits = 0, force_rank = 0;
     int partition = LIFE_PARTITION_CART, sparse = 0, have_at = 0, skip_dead = 0;
     long long at_x = 0, at_y = 0; /* --at X,Y */
@@ -425,6 +432,7 @@ int main(int argc, char **argv) {
             }
             have_rule = 1;
         }
+        else if (!strcmp(s, "--population") && more) pop_path = argv[++a];
         else if (!strcmp(s, "--live")) live = 1;
         else if (!strcmp(s, "--rank-mode")) force_rank = 1;
         else if (s[0] != '-' && !cfg_path) cfg_path = s;
@@ -528,6 +536,7 @@ int main(int argc, char **argv) {
     if (rc) die("create", rc);
     if (have_rule && (rc = life_dev_set_rule(d, birth, survive)) != LIFE_OK) die("--rule", rc);
     if (skip_dead && (rc = life_dev_configure(d, LIFE_OPT_SKIP_DEAD, 1)) != LIFE_OK) die("--skip-dead", rc);
+    if (pop_path && (rc = life_dev_configure(d, LIFE_OPT_POPULATION, 1)) != LIFE_OK) die("--population", rc);
     const int writer = !rank_mode || rank == root; /* the process that writes frames and prints */
     uint8_t *grid = NULL; /* packed rows: bits frames */
     char *body = NULL;    /* VTK cell text */
@@ -573,6 +582,21 @@ int main(int argc, char **argv) {
      * collects + VTK writes and every generation.  Generations and frame
      * numbers are absolute: a resumed run continues the dump's sequence and
      * --steps counts from generation 0. */
+    /* --population: generation gen0 now, the others after each step call (collective in rank mode) */
+    enum { POP_CHUNK = 65536 }; /* generations per step call at most while recording */
+    FILE *pop_file = NULL;
+    int64_t *pop = NULL;
+    if (pop_path) {
+        const int64_t n0 = life_dev_live_count(d);
+        if (n0 < 0) die("--population", (int)n0);
+        pop = (int64_t *)malloc(POP_CHUNK * sizeof *pop);
+        if (!pop) die("host trace", LIFE_ENOMEM);
+        if (writer) {
+            pop_file = fopen(pop_path, "w");
+            if (!pop_file || fprintf(pop_file, "%lld %lld\n", (long long)gen0, (long long)n0) < 0)
+                die(pop_path, LIFE_EIO);
+        }
+    }
     if ((rc = life_dev_barrier(d))) die("barrier", rc);
     const double t0 = now_s();
     char path[64];
@@ -594,12 +618,20 @@ int main(int argc, char **argv) {
             const int64_t to_save = c.save_steps - i % c.save_steps;
             if (to_save < n) n = to_save;
         }
+        if (pop_path && n > POP_CHUNK) n = POP_CHUNK;
         if ((rc = life_dev_step(d, n))) die("step", rc); /* asynchronous */
         if (save && writer &&
             (rc = bits == 2   ? save_density(path, c.nx, c.ny, fx, fy, i, dens)
                   : bits == 1 ? save_bits(path, c.nx, c.ny, i, grid)
                               : save_vtk(path, c.nx, c.ny, body)))
             die(path, rc);
+        if (pop_path) { /* (blocking: after the frame is written) */
+            int64_t got = 0;
+            if ((rc = life_dev_population(d, pop, n, &got)) || got != n) die("population", rc ? rc : LIFE_ESTATE);
+            for (int64_t g = 0; g < n && pop_file; g++)
+                if (fprintf(pop_file, "%lld %lld\n", (long long)(i + g + 1), (long long)pop[g]) < 0)
+                    die(pop_path, LIFE_EIO);
+        }
         i += n;
     }
     if ((rc = life_dev_sync(d))) die("sync", rc);
@@ -610,6 +642,8 @@ int main(int argc, char **argv) {
         const int64_t n = life_dev_live_count(d); /* collective in rank mode */
         if (writer) fprintf(stderr, "live %lld\n", (long long)n);
     }
+    if (pop_file && fclose(pop_file) != 0) die(pop_path, LIFE_EIO);
+    free(pop);
     life_dev_destroy(d);
     free(grid);
     free(body);

@@ -47,6 +47,7 @@ OPT_FLOW_CHUNK = 8
 OPT_DEEP_HALO = 9
 OPT_PIPELINE = 11  # 0 off, 1 automatic, 3..16 row regions per pass (LIFE_OPT_PIPELINE)
 OPT_SKIP_DEAD = 12  # 0 off, 1 run only the tiles whose window may hold a live cell (LIFE_OPT_SKIP_DEAD)
+OPT_POPULATION = 13  # 0 off, 1 record the population of every generation of a step call (LIFE_OPT_POPULATION)
 # LIFE_TEMPORAL_DEPTH(_BYTE): generations per halo exchange of the temporal layouts
 TEMPORAL_DEPTH = {"bit": 32, "byte": 32}
 BLOCK_GENS = {"bit": 12, "byte": 32}  # tiles: default generations per launch at most (LIFE_OPT_BLOCK_GENS)
@@ -58,6 +59,9 @@ TEMPORAL_XAPRON = {"bit": 64, "byte": 32}  # x-apron of the temporal layouts: on
 # B3/S23; life_dev_kernel_work books them, tests/test_isa_rule.py and tests/test_isa.py pin them
 RULE_VALU_PER_PAIR_ROW = 56
 CONWAY_VALU_PER_PAIR_ROW = 22
+# what the census instances of the bit tiles add per pair row and generation: two v_bcnt_u32_b32
+# (csrc/life_kernels.h kPopValuPerPairRow, LIFE_OPT_POPULATION)
+POP_VALU_PER_PAIR_ROW = 2
 RULE_CONWAY = (1 << 3, (1 << 2) | (1 << 3))  # (birth, survive) masks of B3/S23
 
 # Every symbol include/life_mi355x.h declares (checked by tests/test_abi.py).
@@ -74,7 +78,7 @@ ABI_SYMBOLS = (
     "life_dev_clear", "life_dev_set_cells", "life_dev_gather_rect", "life_dev_gather_density",
     "life_dev_upload_bits", "life_dev_set_rect",
     "life_rule_parse", "life_rule_format", "life_dev_set_rule", "life_dev_get_rule",
-    "life_dev_activity",
+    "life_dev_activity", "life_dev_population",
 )
 PATHS = {0: "none", 1: "onegen", 2: "tiles", 3: "flow", 5: "small", 6: "skip"}
 
@@ -187,6 +191,8 @@ def _lib():
             L.life_dev_get_rule.argtypes = [vp, P(u32), P(u32)]
         if hasattr(L, "life_dev_activity"):  # absent from builds that predate LIFE_OPT_SKIP_DEAD (A/B runs)
             L.life_dev_activity.argtypes = [vp] + [P(i64)] * 4
+        if hasattr(L, "life_dev_population"):  # absent from builds that predate LIFE_OPT_POPULATION (A/B runs)
+            L.life_dev_population.argtypes = [vp, P(i64), i64, P(i64)]
         L.life_tune.argtypes = [i32, i32, i32]
         L.life_tune_temporal.argtypes = [i32, i32]
         L.life_measure_copy.argtypes = [i32, i64, i32, P(ctypes.c_double)]
@@ -329,7 +335,7 @@ class Life:
 
     def __init__(self, nx: int, ny: int, shards: int = 1, kernel="bit", dims=(0, 0),
                  transport: int = XPORT_AUTO, small_grid: bool = True, overlap: bool = True, flow=None,
-                 window=None, rule=None, skip_dead: bool = False, _handle=None):
+                 window=None, rule=None, skip_dead: bool = False, population: bool = False, _handle=None):
         self.nx, self.ny = int(nx), int(ny)
         self.kernel = kernel_id(kernel)
         self._h = ctypes.c_void_p()
@@ -363,6 +369,10 @@ class Life:
         # (LIFE_OPT_SKIP_DEAD; no effect on devices that do not qualify)
         if skip_dead:
             self.configure(OPT_SKIP_DEAD, 1)
+        # population: every step call records the live cells after each of its
+        # generations (LIFE_OPT_POPULATION; population() reads them)
+        if population:
+            self.configure(OPT_POPULATION, 1)
 
     def configure(self, option: int, value: int) -> None:
         _check(_lib().life_dev_configure(self._h, option, value), "configure")
@@ -546,6 +556,18 @@ class Life:
         v = [ctypes.c_int64() for _ in range(4)]
         _check(_lib().life_dev_activity(self._h, *[ctypes.byref(x) for x in v]), "activity")
         return tuple(x.value for x in v)
+
+    def population(self) -> np.ndarray:
+        """The live cells of the whole grid after each generation of the last
+        step call (life_dev_population; blocking): an int64 array, empty when
+        that call recorded nothing (LIFE_OPT_POPULATION off, step(0), no call)."""
+        n = ctypes.c_int64()
+        _check(_lib().life_dev_population(self._h, None, 0, ctypes.byref(n)), "population")
+        out = np.zeros(n.value, dtype=np.int64)
+        if n.value:
+            _check(_lib().life_dev_population(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n.value,
+                                              None), "population")
+        return out
 
     def flow_active(self) -> bool:
         return self.last_path() == "flow"
