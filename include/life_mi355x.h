@@ -589,6 +589,82 @@ int life_measure_copy(int device, int64_t bytes, int reps, double *gbps);
 /* life_free (life_cart.c:146-157). */
 void life_dev_destroy(life_dev *d);
 
+/* ---- Batches: many independent small universes stepped in one launch
+ * (DESIGN.md 5.11).  A life_batch holds `count` periodic nx x ny universes of
+ * one shape on one GPU, in its own storage (natural 32-cell words, bit k of
+ * word j = cell 32j + k, ceil(nx/32) words per row, no aprons), and one
+ * stream: every call below is ordered on it, so step -> census / gather needs
+ * no sync by the caller.  No reference counterpart (the reference steps one
+ * grid).  Two tiers, by shape alone:
+ *  LIFE_BATCH_TIER_WAVE   1 <= nx <= 128, 1 <= ny <= 64: one universe per
+ *                         wave, the whole state in its registers, no barrier
+ *                         and no LDS exchange per generation; any rule
+ *                         life_dev_set_rule accepts; LIFE_BATCH_OPT_SETTLE.
+ *  LIFE_BATCH_TIER_GROUP  every other shape the one-workgroup register kernel
+ *                         of the small-grid path takes (at most 2048 cells
+ *                         wide, strips of R rows dividing ny, R one of 1 2 3 4
+ *                         5 6 8 10 12 16 20 25 32, at most 1024 / Wp strips,
+ *                         Wp = the words per row rounded up to a power of
+ *                         two): one universe per workgroup, B3/S23 only.
+ * Any other shape is LIFE_EINVAL, with a message naming both limits. */
+typedef struct life_batch life_batch; /* opaque: device memory and one stream */
+#define LIFE_BATCH_TIER_WAVE 1
+#define LIFE_BATCH_TIER_GROUP 2
+/* Host only (no GPU needed): the tier of a shape and the bytes one universe
+ * takes on the device, 4 * ceil(nx/32) * ny.  Either out pointer may be NULL.
+ * LIFE_EINVAL with a message for a shape in neither tier. */
+int life_batch_query(int64_t nx, int64_t ny, int *tier, int64_t *bytes_per_universe);
+/* count >= 1 universes, all dead, on HIP device `device`, rule B3/S23,
+ * generation 0.  Blocking.  LIFE_EINVAL: the shape (as life_batch_query), count
+ * < 1, out NULL; LIFE_EHIP: no such device; LIFE_ENOMEM. */
+int life_batch_create(int64_t nx, int64_t ny, int64_t count, int device, life_batch **out);
+void life_batch_destroy(life_batch *b);
+/* Universes [first, first + n) from / to n dense grids of ny * nx bytes each,
+ * row-major, one after the other (upload: nonzero = alive; gather: 0 / 1).
+ * Both block until `grids` may be reused / is filled.  upload resets the
+ * settled flag of the universes it writes and of no other; one that covers all
+ * universes restarts the generation counter at 0.  LIFE_EINVAL: first < 0, n <
+ * 0, first + n > count, grids NULL with n > 0. */
+int life_batch_upload(life_batch *b, int64_t first, int64_t n, const uint8_t *grids);
+int life_batch_gather(life_batch *b, int64_t first, int64_t n, uint8_t *grids);
+/* Every universe filled at random: universe u is bit for bit what
+ * life_dev_fill_random(seed + u mod 2^64, thr32) gives an nx x ny grid.
+ * Asynchronous.  Resets every settled flag and the generation counter. */
+int life_batch_fill_random(life_batch *b, uint64_t seed, uint32_t thr32);
+/* The rule of the following steps (masks as life_rule_parse gives them); the
+ * states are untouched, every settled flag is cleared (a state settled under
+ * one rule is not settled under another).  LIFE_EINVAL, with a message: bits
+ * above 8, B0 rules, any rule other than B3/S23 on a group-tier batch. */
+int life_batch_set_rule(life_batch *b, uint32_t birth, uint32_t survive);
+int life_batch_get_rule(life_batch *b, uint32_t *birth, uint32_t *survive);
+/* LIFE_BATCH_OPT_SETTLE (wave tier, value 0 / 1, default 0): while on, a wave
+ * compares its universe after each generation of a step call, from the call's
+ * second on, with the state two generations earlier.  At the first generation
+ * g with S_g == S_(g-2) (still lifes and period-2 oscillators) it records the
+ * absolute generation (life_batch_settled), runs (n - g) mod 2 more generations
+ * and exits: the state it leaves is exactly the state after all n.  A
+ * universe already flagged runs n mod 2 generations in later calls.  States
+ * are bit-identical with the option on and off.  LIFE_EINVAL: a group-tier
+ * batch, any other option or value. */
+#define LIFE_BATCH_OPT_SETTLE 1
+int life_batch_configure(life_batch *b, int option, int value);
+/* All universes advance `generations`.  Asynchronous (one launch); 0 is a
+ * no-op; LIFE_EINVAL when negative or above INT32_MAX. */
+int life_batch_step(life_batch *b, int64_t generations);
+/* Per universe, `count` entries each, either may be NULL: the live cells, and
+ * life_dev_checksum's sum evaluated with the universe's own nx (the sum over
+ * its live (x, y) of mix64(y * nx + x + 1)).  Blocking. */
+int life_batch_census(life_batch *b, int64_t *live, uint64_t *checksum);
+/* Per universe, `count` entries: the absolute generation (on the counter of
+ * life_batch_generation) at which LIFE_BATCH_OPT_SETTLE found it settled, -1
+ * if it has not.  Blocking. */
+int life_batch_settled(life_batch *b, int64_t *generation);
+/* Generations stepped since the states were last written as a whole
+ * (creation, life_batch_fill_random, an upload of all universes).  Host only. */
+int life_batch_generation(life_batch *b, int64_t *generation);
+/* Waits for the batch's stream. */
+int life_batch_sync(life_batch *b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,277 @@
+// life_batch.hip -- the life_batch runtime (include/life_mi355x.h, DESIGN.md
+// 5.11): `count` independent universes of one shape on one GPU, one stream.
+// The plan is life::batch_plan (life_plan.cpp), the kernels are
+// life_batch_kernels.hip.  Every call sets the batch's device and enqueues on
+// its stream; the blocking ones wait for it.
+#include <limits.h>
+
+#include "life_batch_kernels.h"
+#include "life_dev_internal.h"
+
+using namespace life::rt;
+
+struct life_batch {
+    int64_t nx = 0, ny = 0, count = 0;
+    int device = 0;
+    life::BatchPlan plan;
+    hipStream_t stream = nullptr;
+    uint32_t *cells = nullptr;
+    int64_t *settled = nullptr;  // per universe: -1, or the generation LIFE_BATCH_OPT_SETTLE found it settled at
+    unsigned long long *census = nullptr;  // live[count], checksum[count]
+    bool census_valid = false;             // of the current states
+    uint8_t *stage = nullptr;              // dense staging of upload / gather (grows on demand)
+    size_t stage_bytes = 0;
+    uint32_t birth = life::kConwayBirth, survive = life::kConwaySurvive;
+    bool table = false;
+    life::RuleWords words{};
+    bool settle = false;
+    int64_t generation = 0;
+};
+
+namespace {
+
+size_t words_of(const life_batch *b, int64_t n) { return (size_t)n * (size_t)(b->plan.bytes / 4); }
+
+int stage_for(life_batch *b, size_t bytes) {
+    if (b->stage_bytes >= bytes) return LIFE_OK;
+    if (b->stage) HIPCHK(hipFree(b->stage));
+    b->stage = nullptr;
+    b->stage_bytes = 0;
+    HIPCHK(hipMalloc(&b->stage, bytes));
+    b->stage_bytes = bytes;
+    return LIFE_OK;
+}
+
+int range_ok(const life_batch *b, int64_t first, int64_t n, const void *grids, const char *what) {
+    if (first < 0 || n < 0 || first > b->count || n > b->count - first || (n > 0 && !grids)) {
+        set_err("%s: universes [%lld, %lld + %lld) of %lld%s", what, (long long)first, (long long)first, (long long)n,
+                (long long)b->count, n > 0 && !grids ? ", no grids" : "");
+        return LIFE_EINVAL;
+    }
+    return LIFE_OK;
+}
+
+// settled flags of universes [first, first + n) back to -1
+int clear_settled(life_batch *b, int64_t first, int64_t n) {
+    if (n > 0) HIPCHK(hipMemsetAsync(b->settled + first, 0xFF, sizeof(int64_t) * (size_t)n, b->stream));
+    return LIFE_OK;
+}
+
+void free_batch(life_batch *b) {
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->cells) (void)hipFree(b->cells);
+    if (b->settled) (void)hipFree(b->settled);
+    if (b->census) (void)hipFree(b->census);
+    if (b->stage) (void)hipFree(b->stage);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    delete b;
+}
+
+int create(life_batch *b) {
+    int ndev = 0;
+    const hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev < 1) {
+        set_err("no HIP device: %s", hipGetErrorString(e));
+        return LIFE_EHIP;
+    }
+    if (b->device < 0 || b->device >= ndev) {
+        set_err("batch: device %d of %d", b->device, ndev);
+        return LIFE_EHIP;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    const size_t bytes = (size_t)b->plan.bytes * (size_t)b->count;
+    HIPCHK(hipMalloc(&b->cells, bytes));
+    HIPCHK(hipMalloc(&b->settled, sizeof(int64_t) * (size_t)b->count));
+    HIPCHK(hipMalloc(&b->census, 2 * sizeof(unsigned long long) * (size_t)b->count));
+    HIPCHK(hipMemsetAsync(b->cells, 0, bytes, b->stream));
+    CHK(clear_settled(b, 0, b->count));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int life_batch_create(int64_t nx, int64_t ny, int64_t count, int device, life_batch **out) {
+    if (!out) return LIFE_EINVAL;
+    *out = nullptr;
+    const life::BatchPlan p = life::batch_plan(nx, ny);
+    if (p.tier == 0) {
+        set_err("%s", p.why);
+        return LIFE_EINVAL;
+    }
+    // one workgroup per universe (group tier) must fit the grid's x
+    if (count < 1 || count > INT_MAX) {
+        set_err("batch: count %lld (1 .. %d)", (long long)count, INT_MAX);
+        return LIFE_EINVAL;
+    }
+    life_batch *b = new life_batch;
+    b->nx = nx;
+    b->ny = ny;
+    b->count = count;
+    b->device = device;
+    b->plan = p;
+    const int rc = create(b);
+    if (rc != LIFE_OK) {
+        free_batch(b);
+        return rc;
+    }
+    *out = b;
+    return LIFE_OK;
+}
+
+void life_batch_destroy(life_batch *b) {
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    free_batch(b);
+}
+
+int life_batch_upload(life_batch *b, int64_t first, int64_t n, const uint8_t *grids) {
+    if (!b) return LIFE_EINVAL;
+    CHK(range_ok(b, first, n, grids, "life_batch_upload"));
+    if (n == 0) return LIFE_OK;
+    HIPCHK(hipSetDevice(b->device));
+    const size_t bytes = (size_t)n * (size_t)(b->nx * b->ny);
+    CHK(stage_for(b, bytes));
+    // `grids` is the caller's pageable memory: the copy is waited for before
+    // this call returns, so the caller may reuse it at once
+    HIPCHK(hipMemcpyAsync(b->stage, grids, bytes, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(life::launch_batch_import(b->plan, b->nx, b->ny, n, b->stage, b->cells + words_of(b, first), b->stream));
+    CHK(clear_settled(b, first, n));
+    b->census_valid = false;
+    if (n == b->count) b->generation = 0;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+int life_batch_gather(life_batch *b, int64_t first, int64_t n, uint8_t *grids) {
+    if (!b) return LIFE_EINVAL;
+    CHK(range_ok(b, first, n, grids, "life_batch_gather"));
+    if (n == 0) return LIFE_OK;
+    HIPCHK(hipSetDevice(b->device));
+    const size_t bytes = (size_t)n * (size_t)(b->nx * b->ny);
+    CHK(stage_for(b, bytes));
+    HIPCHK(life::launch_batch_export(b->plan, b->nx, b->ny, n, b->cells + words_of(b, first), b->stage, b->stream));
+    HIPCHK(hipMemcpyAsync(grids, b->stage, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+int life_batch_fill_random(life_batch *b, uint64_t seed, uint32_t thr32) {
+    if (!b) return LIFE_EINVAL;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(life::launch_batch_fill(b->plan, b->nx, b->ny, b->count, seed, thr32, b->cells, b->stream));
+    CHK(clear_settled(b, 0, b->count));
+    b->census_valid = false;
+    b->generation = 0;
+    return LIFE_OK;
+}
+
+int life_batch_set_rule(life_batch *b, uint32_t birth, uint32_t survive) {
+    if (!b) return LIFE_EINVAL;
+    if ((birth | survive) & ~life::kRuleMask) {
+        set_err("rule masks 0x%x / 0x%x: bits above 8", birth, survive);
+        return LIFE_EINVAL;
+    }
+    char name[24];
+    life::rule_format(birth, survive, name);
+    if (birth & 1u) {
+        set_err("rule %s: B0 rules are not supported (padding bits and idle lanes must stay dead)", name);
+        return LIFE_EINVAL;
+    }
+    const bool conway = birth == life::kConwayBirth && survive == life::kConwaySurvive;
+    if (!conway && b->plan.tier != LIFE_BATCH_TIER_WAVE) {
+        set_err("rule %s: a group-tier batch (%lld x %lld) runs B3/S23 only (rules are a feature of the wave tier)", name,
+                (long long)b->nx, (long long)b->ny);
+        return LIFE_EINVAL;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    CHK(clear_settled(b, 0, b->count));
+    b->birth = birth;
+    b->survive = survive;
+    b->table = !conway;
+    if (b->table) b->words = life::rule_words(birth, survive);
+    return LIFE_OK;
+}
+
+int life_batch_get_rule(life_batch *b, uint32_t *birth, uint32_t *survive) {
+    if (!b) return LIFE_EINVAL;
+    if (birth) *birth = b->birth;
+    if (survive) *survive = b->survive;
+    return LIFE_OK;
+}
+
+int life_batch_configure(life_batch *b, int option, int value) {
+    if (!b) return LIFE_EINVAL;
+    if (option != LIFE_BATCH_OPT_SETTLE || (value != 0 && value != 1)) {
+        set_err("life_batch_configure: option %d value %d", option, value);
+        return LIFE_EINVAL;
+    }
+    if (b->plan.tier != LIFE_BATCH_TIER_WAVE) {
+        set_err("LIFE_BATCH_OPT_SETTLE: a group-tier batch (%lld x %lld) has no settle detection", (long long)b->nx,
+                (long long)b->ny);
+        return LIFE_EINVAL;
+    }
+    b->settle = value != 0;
+    return LIFE_OK;
+}
+
+int life_batch_step(life_batch *b, int64_t generations) {
+    if (!b) return LIFE_EINVAL;
+    if (generations < 0 || generations > INT32_MAX) {
+        set_err("life_batch_step: %lld generations (0 .. %d)", (long long)generations, INT32_MAX);
+        return LIFE_EINVAL;
+    }
+    if (generations == 0) return LIFE_OK;
+    HIPCHK(hipSetDevice(b->device));
+    if (b->plan.tier == LIFE_BATCH_TIER_WAVE)
+        HIPCHK(life::launch_batch_wave(b->plan, b->nx, b->ny, b->count, b->cells, generations,
+                                       b->table ? &b->words : nullptr, b->settle, b->settled, b->generation,
+                                       b->stream));
+    else
+        HIPCHK(life::launch_batch_group(b->plan, b->nx, b->ny, b->count, b->cells, generations, b->stream));
+    b->generation += generations;
+    b->census_valid = false;
+    return LIFE_OK;
+}
+
+int life_batch_census(life_batch *b, int64_t *live, uint64_t *checksum) {
+    if (!b) return LIFE_EINVAL;
+    HIPCHK(hipSetDevice(b->device));
+    unsigned long long *d_live = b->census, *d_sum = b->census + b->count;
+    if (!b->census_valid) {
+        HIPCHK(life::launch_batch_census(b->plan, b->nx, b->ny, b->count, b->cells, d_live, d_sum, b->stream));
+        b->census_valid = true;
+    }
+    const size_t bytes = sizeof(unsigned long long) * (size_t)b->count;
+    if (live) HIPCHK(hipMemcpyAsync(live, d_live, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (checksum) HIPCHK(hipMemcpyAsync(checksum, d_sum, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+int life_batch_settled(life_batch *b, int64_t *generation) {
+    if (!b || !generation) return LIFE_EINVAL;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipMemcpyAsync(generation, b->settled, sizeof(int64_t) * (size_t)b->count, hipMemcpyDeviceToHost,
+                          b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+int life_batch_generation(life_batch *b, int64_t *generation) {
+    if (!b || !generation) return LIFE_EINVAL;
+    *generation = b->generation;
+    return LIFE_OK;
+}
+
+int life_batch_sync(life_batch *b) {
+    if (!b) return LIFE_EINVAL;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+}  // extern "C"

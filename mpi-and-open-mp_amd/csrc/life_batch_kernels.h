@@ -1,0 +1,39 @@
+// life_batch_kernels.h -- launchers of the batch unit (life_batch_kernels.hip):
+// the two stencil tiers of life_batch_step and the batch's data movement.
+// Every launcher is asynchronous on `s`.  `cells` is the batch storage of
+// life::BatchPlan: universe u starts p.bytes * u bytes in.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "life_host.h"
+
+#pragma GCC visibility push(hidden)
+
+namespace life {
+
+// Wave tier: `gens` >= 1 generations of universes [0, count).  rule null:
+// B3/S23.  settle: the detection of LIFE_BATCH_OPT_SETTLE, with settled[u] the
+// universe's flag (-1, or the generation it settled at) and gen0 the batch's
+// generation before this call; off, `settled` is not touched.
+hipError_t launch_batch_wave(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
+                             const RuleWords *rule, bool settle, int64_t *settled, int64_t gen0, hipStream_t s);
+// Group tier (B3/S23): one workgroup per universe.
+hipError_t launch_batch_group(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
+                              int64_t gens, hipStream_t s);
+// live[u] / sum[u] of universes [0, count): the live cells and the checksum of
+// life_dev_checksum with the universe's own nx.
+hipError_t launch_batch_census(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, const uint32_t *cells,
+                               unsigned long long *live, unsigned long long *sum, hipStream_t s);
+// n universes from `cells` on: dense bytes (ny * nx per universe) in and out
+hipError_t launch_batch_import(const BatchPlan &p, int64_t nx, int64_t ny, int64_t n, const uint8_t *dense,
+                               uint32_t *cells, hipStream_t s);
+hipError_t launch_batch_export(const BatchPlan &p, int64_t nx, int64_t ny, int64_t n, const uint32_t *cells,
+                               uint8_t *dense, hipStream_t s);
+// universe u = life_dev_fill_random(seed + u, thr32) of an nx x ny grid
+hipError_t launch_batch_fill(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint64_t seed, uint32_t thr32,
+                             uint32_t *cells, hipStream_t s);
+
+}  // namespace life
+
+#pragma GCC visibility pop

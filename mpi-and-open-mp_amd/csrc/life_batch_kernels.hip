@@ -1,0 +1,395 @@
+// life_batch_kernels.hip -- the kernels of life_batch (gfx950): many
+// independent small periodic universes of one shape, stepped in one launch
+// (DESIGN.md 5.11).
+//
+// Storage (the batch's own): natural 32-cell words, bit k of word j = cell
+// 32j + k, W = ceil(nx/32) words per row, ny rows, universes W * ny words
+// apart; no aprons, no pair interleave: every wrap happens in the kernels.
+// The bits at and beyond nx of a row's last word are zero after every writer.
+// A step call reads a universe into registers once and writes it back in place
+// at the end: exactly one wave (wave tier) or workgroup (group tier) owns it.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+
+#include <algorithm>
+
+#include "life_batch_kernels.h"
+#include "life_bitops.h"
+
+namespace life {
+namespace {
+
+constexpr uint32_t kKeepMux = ((0xF0 & 0xCC) | (~0xCC & 0xAA)) & 0xFF;  // (a & b) | (c & ~b)
+
+// The x wrap of a row whose last word holds q = nx - 32 (W - 1) cells, 1 <= q
+// <= 32 (lane-uniform).  Word 0's left neighbour word must carry cell nx - 1 at
+// bit 31: the last word shifted up by lsh.  The last word takes cell 0 at bit
+// q before the sums (qs; above it: don't-care bits, masked off by `keep` after
+// the rule), and word 0 as its right neighbour word when q == 32.
+struct XWrap {
+    uint32_t keep, lsh, qs;
+    __device__ __forceinline__ explicit XWrap(int nx, int W) {
+        const int q = nx - 32 * (W - 1);
+        keep = q < 32 ? (1u << q) - 1u : 0xFFFFFFFFu;
+        lsh = (uint32_t)((32 - q) & 31);
+        qs = (uint32_t)(q & 31);
+    }
+};
+
+template <class RP>
+__device__ __forceinline__ RP make_rule(const RuleWords &w);
+template <>
+__device__ __forceinline__ ConwayRule make_rule<ConwayRule>(const RuleWords &) {
+    return ConwayRule{};
+}
+template <>
+__device__ __forceinline__ TableRule make_rule<TableRule>(const RuleWords &w) {
+    return TableRule(w);
+}
+
+// ------------------------------------------------------------------ wave tier
+// One universe per wave, one row per lane (ny <= 64), the row's W <= 4 words in
+// registers.  A generation: per word the 2-bit horizontal sums (the neighbour
+// words are the lane's own registers: two funnel shifts and a full adder; the
+// x wrap as XWrap), the sums of the rows above and below by ds_bpermute from
+// the lanes (y - 1) mod ny and (y + 1) mod ny (four per word), the rule.  No
+// LDS allocation, no barrier: the waves of a workgroup never meet.  Lanes at
+// and beyond ny hold zeros and read themselves, so they stay zero under any
+// rule without B0 and a wave-wide vote sees the universe alone.
+struct BWArgs {
+    uint32_t *cells;
+    int64_t *settled;
+    int64_t count, gen0;
+    int32_t nx, ny, gens;
+    RuleWords rule;
+};
+
+template <int W, class RP, bool SETTLE>
+__global__ __launch_bounds__(64 * kBatchWaves) void batch_wave_kernel(BWArgs a) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t u = (int64_t)blockIdx.x * kBatchWaves + (int64_t)(threadIdx.x >> 6);
+    if (u >= a.count) return;  // the whole wave
+    const RP rp = make_rule<RP>(a.rule);
+    const int ny = a.ny;
+    const bool active = lane < ny;
+    const int up = !active ? lane : lane == 0 ? ny - 1 : lane - 1;
+    const int dn = !active ? lane : lane + 1 == ny ? 0 : lane + 1;
+    const int addr_up = up << 2, addr_dn = dn << 2;
+    const XWrap xw(a.nx, W);
+    uint32_t *row = a.cells + ((size_t)u * (size_t)ny + (size_t)lane) * W;
+
+    uint32_t v[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) v[j] = active ? row[j] : 0u;
+
+    int gens = a.gens;
+    bool detect = false;
+    if (SETTLE) {
+        detect = a.settled[u] < 0;
+        if (!detect) gens &= 1;  // settled in an earlier call: the state has period 1 or 2
+    }
+    uint32_t p1[SETTLE ? W : 1], p2[SETTLE ? W : 1];  // S_(g-1), S_(g-2)
+    if (SETTLE) {
+#pragma unroll
+        for (int j = 0; j < W; ++j) p1[j] = p2[j] = v[j];
+    }
+    for (int g = 1; g <= gens; ++g) {
+        uint32_t s0[W], s1[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const uint32_t l = j == 0 ? v[W - 1] << xw.lsh : v[j - 1];
+            const uint32_t r = j == W - 1 ? v[0] : v[j + 1];
+            uint32_t c = v[j];
+            if (j == W - 1) c = b3<kKeepMux>(c, xw.keep, v[0] << xw.qs);
+            BitEnc::fa(__builtin_amdgcn_alignbit(c, l, 31), c, __builtin_amdgcn_alignbit(r, c, 1), s0[j], s1[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const uint32_t a0 = bperm(addr_up, s0[j]), a1 = bperm(addr_up, s1[j]);
+            const uint32_t d0 = bperm(addr_dn, s0[j]), d1 = bperm(addr_dn, s1[j]);
+            v[j] = rp(a0, a1, s0[j], s1[j], d0, d1, v[j]);
+        }
+        v[W - 1] &= xw.keep;
+        if (SETTLE && detect) {
+            if (g >= 2) {
+                uint32_t diff = 0;
+#pragma unroll
+                for (int j = 0; j < W; ++j) diff |= v[j] ^ p2[j];
+                if (__builtin_amdgcn_ballot_w64(diff != 0u) == 0ull) {  // S_g == S_(g-2), the whole wave agrees
+                    if (lane == 0) a.settled[u] = a.gen0 + g;
+                    detect = false;
+                    gens = g + ((gens - g) & 1);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                p2[j] = p1[j];
+                p1[j] = v[j];
+            }
+        }
+    }
+    if (!active) return;
+#pragma unroll
+    for (int j = 0; j < W; ++j) row[j] = v[j];
+}
+
+template <int W, class RP>
+hipError_t launch_wave(const BWArgs &a, bool settle, unsigned blocks, hipStream_t s) {
+    if (settle)
+        batch_wave_kernel<W, RP, true><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
+    else
+        batch_wave_kernel<W, RP, false><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+// ----------------------------------------------------------------- group tier
+// One universe per workgroup: the technique of the small-grid register kernel
+// (life_kernels.hip rsmall_kernel without its window) on the batch storage.
+// A wave is split into 64 / Wp lane groups (Wp = W rounded up to a power of
+// two), each a strip of R consecutive rows, one word column per lane; ns = ny
+// / R strips.  Per generation a lane computes the sums of its R rows
+// (neighbour words by ds_bpermute inside the group, the x wrap as XWrap),
+// publishes those of its first and last row in LDS, one barrier, reads the
+// strip above's last and the strip below's first (periodic in y), and applies
+// B3/S23 to its rows.  The exchange is double-buffered by the generation's
+// parity: a slot is rewritten two generations later, behind the next barrier.
+struct BGArgs {
+    uint32_t *cells;
+    int32_t nx, ny, W, lgWp, gens, ns;
+};
+
+template <int R>
+__global__ __launch_bounds__(kBatchGroupThreads) void batch_group_kernel(BGArgs a) {
+    __shared__ uint32_t xch[2][4][kBatchGroupThreads];  // [parity][top s0/s1, bottom s0/s1][thread]
+    const int t = (int)threadIdx.x;
+    const int Wp = 1 << a.lgWp, W = a.W;
+    const int j = t & (Wp - 1);  // word column
+    const int st = t >> a.lgWp;  // strip
+    const bool active = st < a.ns && j < W;
+    const int base = (t & 63) & ~(Wp - 1);  // first lane of this lane group
+    const int jl = j == 0 ? W - 1 : j - 1, jr = j + 1 >= W ? 0 : j + 1;
+    const int addr_l = (base + jl) << 2, addr_r = (base + jr) << 2;
+    const XWrap xw(a.nx, W);
+    const bool last = j == W - 1;
+    const uint32_t keep = last ? xw.keep : 0xFFFFFFFFu;
+    const uint32_t lsh = j == 0 ? xw.lsh : 0u;
+    const int sa = st == 0 ? a.ns - 1 : st - 1, sb = st + 1 >= a.ns ? 0 : st + 1;
+    const int ta = ((sa << a.lgWp) + j) & (kBatchGroupThreads - 1), tb = ((sb << a.lgWp) + j) & (kBatchGroupThreads - 1);
+    uint32_t *uni = a.cells + (size_t)blockIdx.x * (size_t)W * (size_t)a.ny;
+    const int y0 = st * R;
+
+    uint32_t v[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) v[r] = active ? uni[(size_t)(y0 + r) * W + j] : 0u;
+    auto hsum = [&](uint32_t c, uint32_t &s0, uint32_t &s1) {
+        const uint32_t l = bperm(addr_l, c) << lsh;
+        const uint32_t rw = bperm(addr_r, c);
+        c = b3<kKeepMux>(c, keep, rw << xw.qs);  // the last word gets cell 0 at bit q
+        BitEnc::fa(__builtin_amdgcn_alignbit(c, l, 31), c, __builtin_amdgcn_alignbit(rw, c, 1), s0, s1);
+    };
+    for (int g = 0; g < a.gens; ++g) {
+        const int par = g & 1;
+        uint32_t h0[R], h1[R];
+        hsum(v[0], h0[0], h1[0]);
+        if (R > 1) hsum(v[R - 1], h0[R - 1], h1[R - 1]);
+        xch[par][0][t] = h0[0];
+        xch[par][1][t] = h1[0];
+        xch[par][2][t] = h0[R - 1];
+        xch[par][3][t] = h1[R - 1];
+        __syncthreads();
+        const uint32_t a0 = xch[par][2][ta], a1 = xch[par][3][ta];
+        const uint32_t d0 = xch[par][0][tb], d1 = xch[par][1][tb];
+#pragma unroll
+        for (int r = 1; r < R - 1; ++r) hsum(v[r], h0[r], h1[r]);
+#pragma unroll
+        for (int r = 1; r < R - 1; ++r)
+            v[r] = BitEnc::rule1(h0[r - 1], h1[r - 1], h0[r], h1[r], h0[r + 1], h1[r + 1], v[r]) & keep;
+        if (R == 1) {
+            v[0] = BitEnc::rule1(a0, a1, h0[0], h1[0], d0, d1, v[0]) & keep;
+        } else {
+            v[0] = BitEnc::rule1(a0, a1, h0[0], h1[0], h0[1], h1[1], v[0]) & keep;
+            v[R - 1] = BitEnc::rule1(h0[R - 2], h1[R - 2], h0[R - 1], h1[R - 1], d0, d1, v[R - 1]) & keep;
+        }
+    }
+    if (!active) return;
+#pragma unroll
+    for (int r = 0; r < R; ++r) uni[(size_t)(y0 + r) * W + j] = v[r];
+}
+
+// ------------------------------------------------------------- data movement
+// (the definitions of life_io.hip's fill and census, per universe)
+__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ uint64_t cell_mix(uint64_t v) {
+    v *= 0x9E3779B97F4A7C15ull;
+    return v ^ (v >> 29);
+}
+
+// cells of word j of an nx-wide row
+__device__ __forceinline__ int row_cells(int64_t nx, int64_t j) { return nx - 32 * j < 32 ? (int)(nx - 32 * j) : 32; }
+
+// One thread per word, grid-stride: word i = (universe, row, word column).
+struct WordAt {
+    int64_t u, y, j;
+    __device__ __forceinline__ WordAt(int64_t i, int64_t W, int64_t ny) : u(i / (W * ny)), y(i / W % ny), j(i % W) {}
+};
+
+__global__ void batch_import_kernel(const uint8_t *dense, uint32_t *cells, int64_t words, int64_t nx, int64_t ny,
+                                    int64_t W) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (int64_t)gridDim.x * blockDim.x) {
+        const WordAt at(i, W, ny);
+        const uint8_t *src = dense + ((size_t)at.u * (size_t)ny + (size_t)at.y) * (size_t)nx + 32 * at.j;
+        const int n = row_cells(nx, at.j);
+        uint32_t x = 0;
+        for (int k = 0; k < n; ++k) x |= (uint32_t)(src[k] != 0) << k;
+        cells[i] = x;
+    }
+}
+
+__global__ void batch_export_kernel(const uint32_t *cells, uint8_t *dense, int64_t words, int64_t nx, int64_t ny,
+                                    int64_t W) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (int64_t)gridDim.x * blockDim.x) {
+        const WordAt at(i, W, ny);
+        uint8_t *dst = dense + ((size_t)at.u * (size_t)ny + (size_t)at.y) * (size_t)nx + 32 * at.j;
+        const int n = row_cells(nx, at.j);
+        const uint32_t x = cells[i];
+        for (int k = 0; k < n; ++k) dst[k] = (uint8_t)((x >> k) & 1u);
+    }
+}
+
+__global__ void batch_fill_kernel(uint32_t *cells, int64_t words, int64_t nx, int64_t ny, int64_t W, uint64_t seed,
+                                  uint32_t thr) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (int64_t)gridDim.x * blockDim.x) {
+        const WordAt at(i, W, ny);
+        const uint64_t key = splitmix64(seed + (uint64_t)at.u);
+        const uint64_t base = (uint64_t)(at.y * nx + 32 * at.j);
+        const int n = row_cells(nx, at.j);
+        uint32_t x = 0;
+        for (int k = 0; k < n; ++k) x |= (uint32_t)((uint32_t)(splitmix64(key ^ (base + (uint64_t)k)) >> 32) < thr) << k;
+        cells[i] = x;
+    }
+}
+
+// One wave per universe: its lanes walk the universe's words.
+__global__ __launch_bounds__(64 * kBatchWaves) void batch_census_kernel(const uint32_t *cells, unsigned long long *live,
+                                                                        unsigned long long *sum, int64_t count,
+                                                                        int64_t nx, int64_t ny, int64_t W) {
+    const int64_t u = (int64_t)blockIdx.x * kBatchWaves + (int64_t)(threadIdx.x >> 6);
+    if (u >= count) return;
+    const uint32_t *uni = cells + (size_t)u * (size_t)(W * ny);
+    const int64_t q = nx - 32 * (W - 1);
+    unsigned long long c = 0, x = 0;
+    for (int64_t i = threadIdx.x & 63u; i < W * ny; i += 64) {
+        const int64_t y = i / W, j = i % W;
+        uint32_t bits = uni[i];
+        if (j == W - 1 && q < 32) bits &= (1u << q) - 1u;  // (zero already: no writer leaves padding bits)
+        c += __popc(bits);
+        const uint64_t base = (uint64_t)(y * nx + 32 * j) + 1u;
+        while (bits) {
+            const int b = __ffs(bits) - 1;
+            bits &= bits - 1u;
+            x += cell_mix(base + (uint64_t)b);
+        }
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+        c += __shfl_xor(c, s);
+        x += __shfl_xor(x, s);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        live[u] = c;
+        sum[u] = x;
+    }
+}
+
+unsigned word_blocks(int64_t words) { return (unsigned)std::min<int64_t>((words + 255) / 256, 1 << 20); }
+unsigned wave_blocks(int64_t count) { return (unsigned)((count + kBatchWaves - 1) / kBatchWaves); }
+// one workgroup per universe, or per kBatchWaves universes: the grid's x must hold them
+bool grid_ok(int64_t blocks) { return blocks >= 1 && blocks <= INT_MAX; }
+
+}  // namespace
+
+hipError_t launch_batch_wave(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
+                             const RuleWords *rule, bool settle, int64_t *settled, int64_t gen0, hipStream_t s) {
+    if (p.tier != LIFE_BATCH_TIER_WAVE || gens < 1 || gens > INT32_MAX || (settle && !settled) ||
+        !grid_ok((count + kBatchWaves - 1) / kBatchWaves))
+        return hipErrorInvalidValue;
+    BWArgs a{};
+    a.cells = cells;
+    a.settled = settled;
+    a.count = count;
+    a.gen0 = gen0;
+    a.nx = (int32_t)nx;
+    a.ny = (int32_t)ny;
+    a.gens = (int32_t)gens;
+    if (rule) a.rule = *rule;
+    const unsigned blocks = wave_blocks(count);
+    switch (p.words) {
+#define LIFE_BW(N) \
+    case N: return rule ? launch_wave<N, TableRule>(a, settle, blocks, s) : launch_wave<N, ConwayRule>(a, settle, blocks, s);
+        LIFE_BW(1) LIFE_BW(2) LIFE_BW(3) LIFE_BW(4)
+#undef LIFE_BW
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_batch_group(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
+                              int64_t gens, hipStream_t s) {
+    if (p.tier != LIFE_BATCH_TIER_GROUP || gens < 1 || gens > INT32_MAX || !grid_ok(count)) return hipErrorInvalidValue;
+    BGArgs a{};
+    a.cells = cells;
+    a.nx = (int32_t)nx;
+    a.ny = (int32_t)ny;
+    a.W = p.words;
+    a.lgWp = p.lg_wp;
+    a.gens = (int32_t)gens;
+    a.ns = p.strips;
+    // only the waves that own strips (the barrier counts the launched waves)
+    const unsigned threads = 64u * (unsigned)p.waves_per_group;
+    if (threads > (unsigned)kBatchGroupThreads) return hipErrorInvalidValue;
+    switch (p.rows) {
+#define LIFE_BG(N) \
+    case N: batch_group_kernel<N><<<(unsigned)count, threads, 0, s>>>(a); break;
+        LIFE_BG(1) LIFE_BG(2) LIFE_BG(3) LIFE_BG(4) LIFE_BG(5) LIFE_BG(6) LIFE_BG(8) LIFE_BG(10) LIFE_BG(12)
+        LIFE_BG(16) LIFE_BG(20) LIFE_BG(25) LIFE_BG(32)
+#undef LIFE_BG
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_census(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, const uint32_t *cells,
+                               unsigned long long *live, unsigned long long *sum, hipStream_t s) {
+    if (!grid_ok((count + kBatchWaves - 1) / kBatchWaves)) return hipErrorInvalidValue;
+    batch_census_kernel<<<wave_blocks(count), 64 * kBatchWaves, 0, s>>>(cells, live, sum, count, nx, ny, p.words);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_import(const BatchPlan &p, int64_t nx, int64_t ny, int64_t n, const uint8_t *dense,
+                               uint32_t *cells, hipStream_t s) {
+    const int64_t words = n * ny * p.words;
+    if (words < 1) return hipSuccess;
+    batch_import_kernel<<<word_blocks(words), 256, 0, s>>>(dense, cells, words, nx, ny, p.words);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_export(const BatchPlan &p, int64_t nx, int64_t ny, int64_t n, const uint32_t *cells,
+                               uint8_t *dense, hipStream_t s) {
+    const int64_t words = n * ny * p.words;
+    if (words < 1) return hipSuccess;
+    batch_export_kernel<<<word_blocks(words), 256, 0, s>>>(cells, dense, words, nx, ny, p.words);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_fill(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint64_t seed, uint32_t thr32,
+                             uint32_t *cells, hipStream_t s) {
+    const int64_t words = count * ny * p.words;
+    if (words < 1) return hipSuccess;
+    batch_fill_kernel<<<word_blocks(words), 256, 0, s>>>(cells, words, nx, ny, p.words, seed, thr32);
+    return hipGetLastError();
+}
+
+}  // namespace life

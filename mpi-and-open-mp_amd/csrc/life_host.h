@@ -138,6 +138,28 @@ RuleWords rule_words(uint32_t birth, uint32_t survive);
 bool rule_parse(const char *text, uint32_t *birth, uint32_t *survive);
 void rule_format(uint32_t birth, uint32_t survive, char out[24]);
 
+// Batches (life_batch_*): how `count` universes of one shape
+// are stored and launched.  Storage: natural 32-cell words, `words` per row,
+// ny rows, universes `bytes` apart.  Wave tier (nx <= kBatchWaveMaxX, ny <=
+// kBatchWaveMaxY): one universe per wave, one row per lane, kBatchWaves waves
+// per workgroup.  Group tier: one universe per workgroup of lane groups of 2^
+// lg_wp lanes, each a strip of `rows` rows -- the shapes of the small-grid
+// register kernel (life_kernels.hip reg_small_rows: the same strip heights,
+// threads and word limit, restated here so the plan needs no HIP).  tier 0:
+// neither, `why` says so.
+constexpr int64_t kBatchWaveMaxX = 128, kBatchWaveMaxY = 64, kBatchGroupMaxX = 2048;
+constexpr int kBatchWaves = 4, kBatchGroupThreads = 1024;
+struct BatchPlan {
+    int tier = 0;
+    int words = 0;           // per row
+    int64_t bytes = 0;       // per universe
+    int waves_per_group = 0; // waves of a workgroup
+    int universes_per_group = 0;
+    int rows = 0, lg_wp = 0, strips = 0;  // group tier: strip height R, log2 lanes per strip, ny / R
+    char why[400] = {};
+};
+BatchPlan batch_plan(int64_t nx, int64_t ny);
+
 // The dataflow queue head is 32-bit: one launch may hold at most
 // kFlowMaxHead pulls (its items plus one extra pull per resident workgroup).
 // flow_chunk_passes: passes of `tiles` items each one launch of `grid`

@@ -462,7 +462,56 @@ int life_rule_format(uint32_t birth, uint32_t survive, char out[24]) {
     return LIFE_OK;
 }
 
+int life_batch_query(int64_t nx, int64_t ny, int *tier, int64_t *bytes_per_universe) {
+    const life::BatchPlan p = life::batch_plan(nx, ny);
+    if (p.tier == 0) {
+        if (life::rt::set_err) life::rt::set_err("%s", p.why);
+        return LIFE_EINVAL;
+    }
+    if (tier) *tier = p.tier;
+    if (bytes_per_universe) *bytes_per_universe = p.bytes;
+    return LIFE_OK;
+}
+
 }  // extern "C"
+
+// ---- batches (life_host.h)
+life::BatchPlan life::batch_plan(int64_t nx, int64_t ny) {
+    BatchPlan p;
+    auto fail = [&](const char *what) {
+        snprintf(p.why, sizeof p.why,
+                 "batch of %lld x %lld universes: %s (wave tier: nx <= %lld and ny <= %lld; group tier: nx <= %lld and "
+                 "ny = strips x R rows, R in 1 2 3 4 5 6 8 10 12 16 20 25 32, strips x lanes per strip <= %d)",
+                 (long long)nx, (long long)ny, what, (long long)kBatchWaveMaxX, (long long)kBatchWaveMaxY,
+                 (long long)kBatchGroupMaxX, kBatchGroupThreads);
+        return p;
+    };
+    if (nx < 1 || ny < 1) return fail("empty shape");
+    if (nx > kBatchGroupMaxX) return fail("too wide");
+    p.words = (int)((nx + 31) / 32);
+    p.bytes = 4 * (int64_t)p.words * ny;
+    if (nx <= kBatchWaveMaxX && ny <= kBatchWaveMaxY) {
+        p.tier = LIFE_BATCH_TIER_WAVE;
+        p.waves_per_group = kBatchWaves;
+        p.universes_per_group = kBatchWaves;
+        return p;
+    }
+    while ((1 << p.lg_wp) < p.words) ++p.lg_wp;
+    const int64_t strips = kBatchGroupThreads >> p.lg_wp;
+    static const int kRows[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 25, 32};  // life_kernels.hip kRegRows
+    for (int R : kRows)
+        if (ny % R == 0 && ny / R <= strips) {
+            p.tier = LIFE_BATCH_TIER_GROUP;
+            p.rows = R;
+            p.strips = (int)(ny / R);
+            p.waves_per_group = (int)((((int64_t)p.strips << p.lg_wp) + 63) / 64);
+            p.universes_per_group = 1;
+            return p;
+        }
+    p.words = 0;
+    p.bytes = 0;
+    return fail("no strip height fits one workgroup");
+}
 
 namespace {
 // Slots grouped by the time they fall free (a list schedule of a few item

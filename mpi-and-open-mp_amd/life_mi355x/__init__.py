@@ -79,7 +79,13 @@ ABI_SYMBOLS = (
     "life_dev_upload_bits", "life_dev_set_rect",
     "life_rule_parse", "life_rule_format", "life_dev_set_rule", "life_dev_get_rule",
     "life_dev_activity", "life_dev_population",
+    "life_batch_query", "life_batch_create", "life_batch_destroy", "life_batch_upload", "life_batch_gather",
+    "life_batch_fill_random", "life_batch_set_rule", "life_batch_get_rule", "life_batch_configure",
+    "life_batch_step", "life_batch_census", "life_batch_settled", "life_batch_generation", "life_batch_sync",
 )
+BATCH_TIER_WAVE, BATCH_TIER_GROUP = 1, 2  # LIFE_BATCH_TIER_*
+BATCH_TIERS = {BATCH_TIER_WAVE: "wave", BATCH_TIER_GROUP: "group"}
+BATCH_OPT_SETTLE = 1  # LIFE_BATCH_OPT_SETTLE
 PATHS = {0: "none", 1: "onegen", 2: "tiles", 3: "flow", 5: "small", 6: "skip"}
 
 
@@ -193,6 +199,23 @@ def _lib():
             L.life_dev_activity.argtypes = [vp] + [P(i64)] * 4
         if hasattr(L, "life_dev_population"):  # absent from builds that predate LIFE_OPT_POPULATION (A/B runs)
             L.life_dev_population.argtypes = [vp, P(i64), i64, P(i64)]
+        if hasattr(L, "life_batch_create"):  # absent from builds that predate batches (LIFE_MI355X_LIB A/B runs)
+            u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+            L.life_batch_query.argtypes = [i64, i64, P(ctypes.c_int), P(i64)]
+            L.life_batch_create.argtypes = [i64, i64, i64, i32, P(vp)]
+            L.life_batch_destroy.argtypes = [vp]
+            L.life_batch_destroy.restype = None
+            L.life_batch_upload.argtypes = [vp, i64, i64, P(ctypes.c_uint8)]
+            L.life_batch_gather.argtypes = [vp, i64, i64, P(ctypes.c_uint8)]
+            L.life_batch_fill_random.argtypes = [vp, u64, u32]
+            L.life_batch_set_rule.argtypes = [vp, u32, u32]
+            L.life_batch_get_rule.argtypes = [vp, P(u32), P(u32)]
+            L.life_batch_configure.argtypes = [vp, i32, i32]
+            L.life_batch_step.argtypes = [vp, i64]
+            L.life_batch_census.argtypes = [vp, P(i64), P(u64)]
+            L.life_batch_settled.argtypes = [vp, P(i64)]
+            L.life_batch_generation.argtypes = [vp, P(i64)]
+            L.life_batch_sync.argtypes = [vp]
         L.life_tune.argtypes = [i32, i32, i32]
         L.life_tune_temporal.argtypes = [i32, i32]
         L.life_measure_copy.argtypes = [i32, i64, i32, P(ctypes.c_double)]
@@ -292,6 +315,16 @@ def _rule_masks(rule):
         return parse_rule(rule)
     birth, survive = rule
     return int(birth), int(survive)
+
+
+def batch_query(nx: int, ny: int):
+    """(tier, bytes per universe) of a batch of nx x ny universes
+    (life_batch_query, no GPU needed): tier "wave" (one universe per wave, 1 <=
+    nx <= 128, 1 <= ny <= 64) or "group" (one per workgroup, the shapes of the
+    small-grid register kernel); LifeError for a shape in neither."""
+    tier, nbytes = ctypes.c_int(), ctypes.c_int64()
+    _check(_lib().life_batch_query(int(nx), int(ny), ctypes.byref(tier), ctypes.byref(nbytes)), "life_batch_query")
+    return BATCH_TIERS[tier.value], nbytes.value
 
 
 def density_to_thr(density: float) -> int:
@@ -608,6 +641,122 @@ class Life:
     def close(self) -> None:
         if self._h:
             _lib().life_dev_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LifeBatch:
+    """``count`` independent periodic nx x ny universes on one GPU, advanced
+    together by one launch per :meth:`step` (life_batch_*).
+
+    Every call is ordered on the batch's one stream: ``step`` returns at once,
+    and a following ``gather`` / ``live_counts`` / ``checksums`` / ``settled``
+    waits for it.  ``rule``: None (B3/S23), a rulestring or a (birth, survive)
+    pair (wave tier only).  ``settle``: stop a universe early once it repeats
+    with period 1 or 2 (LIFE_BATCH_OPT_SETTLE; wave tier only)."""
+
+    def __init__(self, nx: int, ny: int, count: int, device: int = 0, rule=None, settle: bool = False):
+        self.nx, self.ny, self.count = int(nx), int(ny), int(count)
+        self._h = ctypes.c_void_p()
+        _check(_lib().life_batch_create(self.nx, self.ny, self.count, int(device), ctypes.byref(self._h)),
+               "life_batch_create")
+        self.tier = batch_query(self.nx, self.ny)[0]
+        if rule is not None:
+            self.set_rule(rule)
+        if settle:
+            self.configure(BATCH_OPT_SETTLE, 1)
+
+    def configure(self, option: int, value: int) -> None:
+        _check(_lib().life_batch_configure(self._h, int(option), int(value)), "life_batch_configure")
+
+    def set_rule(self, rule) -> None:
+        """life_batch_set_rule: what :meth:`Life.set_rule` accepts; a rule other
+        than B3/S23 needs a wave-tier batch.  Clears every settled flag."""
+        birth, survive = _rule_masks(rule)
+        if not (0 <= birth < 2**32 and 0 <= survive < 2**32):
+            raise ValueError(f"rule masks {birth}, {survive} are not 32-bit")
+        _check(_lib().life_batch_set_rule(self._h, birth, survive), "life_batch_set_rule")
+
+    @property
+    def rule(self) -> str:
+        b, s = ctypes.c_uint32(), ctypes.c_uint32()
+        _check(_lib().life_batch_get_rule(self._h, ctypes.byref(b), ctypes.byref(s)), "life_batch_get_rule")
+        return format_rule(b.value, s.value)
+
+    @property
+    def generation(self) -> int:
+        """Generations stepped since the states were last written as a whole."""
+        g = ctypes.c_int64()
+        _check(_lib().life_batch_generation(self._h, ctypes.byref(g)), "life_batch_generation")
+        return g.value
+
+    def upload(self, grids, first: int = 0) -> None:
+        """Universes [first, first + n) from an (n, ny, nx) array (nonzero = alive)."""
+        g = np.asarray(grids)
+        if g.ndim != 3 or g.shape[1:] != (self.ny, self.nx):
+            raise ValueError(f"upload: grids shape {g.shape} != (n, {self.ny}, {self.nx})")
+        g = np.ascontiguousarray(g if g.dtype == np.uint8 else g != 0, dtype=np.uint8)
+        _check(_lib().life_batch_upload(self._h, int(first), g.shape[0],
+                                        g.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))), "life_batch_upload")
+
+    def gather(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """Universes [first, first + n) as an (n, ny, nx) uint8 array of 0 / 1
+        (n None: all from `first` on)."""
+        first = int(first)
+        n = self.count - first if n is None else int(n)
+        out = _host_buffer((max(n, 0), self.ny, self.nx))
+        _check(_lib().life_batch_gather(self._h, first, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+               "life_batch_gather")
+        return out
+
+    def fill_random(self, seed: int, density: float = 0.5) -> None:
+        """Universe u becomes what ``Life.fill_random(seed + u, density)`` gives
+        an nx x ny grid (seed + u modulo 2^64)."""
+        _check(_lib().life_batch_fill_random(self._h, int(seed) % 2**64, density_to_thr(density)),
+               "life_batch_fill_random")
+
+    def step(self, generations: int = 1) -> None:
+        _check(_lib().life_batch_step(self._h, int(generations)), "life_batch_step")
+
+    def live_counts(self) -> np.ndarray:
+        """The live cells of every universe (int64, count entries)."""
+        out = np.zeros(self.count, dtype=np.int64)
+        _check(_lib().life_batch_census(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), None),
+               "life_batch_census")
+        return out
+
+    def checksums(self) -> np.ndarray:
+        """``oracle.checksum`` of every universe (uint64, count entries)."""
+        out = np.zeros(self.count, dtype=np.uint64)
+        _check(_lib().life_batch_census(self._h, None, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))),
+               "life_batch_census")
+        return out
+
+    def settled(self) -> np.ndarray:
+        """Per universe the generation at which settle detection found it
+        repeating with period 1 or 2, -1 where it has not (int64)."""
+        out = np.zeros(self.count, dtype=np.int64)
+        _check(_lib().life_batch_settled(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
+               "life_batch_settled")
+        return out
+
+    def sync(self) -> None:
+        _check(_lib().life_batch_sync(self._h), "life_batch_sync")
+
+    def close(self) -> None:
+        if self._h:
+            _lib().life_batch_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __enter__(self):

@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""Throughput of life_batch against the host loop it replaces (DESIGN.md §5.11,
+profiles/batch/README.md).
+
+Batch: LifeBatch.step(n) between two syncs, 50 % soups, settle off.  Baseline:
+one Life(nx, ny) object per universe on the small-grid path, the same soups
+(fill_random(seed + u)) and generations, one step(n) each and a sync of all at
+the end, timed at a count small enough to finish in seconds and scaled per
+universe.  Every timing is the median of --reps runs after one warm-up run of
+the same shape; before timing, the first universes' checksums of both paths
+are compared after the warm-up run.  One JSON line per row on stdout (and in
+--out), a markdown table on stderr.
+
+    python scripts/batch_bench.py --out profiles/batch/batch_bench.jsonl
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "mpi-and-open-mp_amd"))
+
+import life_mi355x as lm  # noqa: E402
+
+ROWS = [((32, 32), (1024, 16384, 262144)), ((64, 64), (1024, 16384, 262144)), ((128, 64), (1024, 16384, 262144)),
+        ((500, 500), (256, 4096))]
+SEED = 1234
+
+
+def timed(fn, sync):
+    sync()
+    t0 = time.perf_counter()
+    fn()
+    sync()
+    return time.perf_counter() - t0
+
+
+def batch_time(nx, ny, count, gens, reps, density=0.5, settle=False):
+    """(median s, min s, max s, settled share) of LifeBatch.step(gens)."""
+    with lm.LifeBatch(nx, ny, count, settle=settle) as b:
+        times = []
+        for rep in range(reps + 1):  # the first is the warm-up
+            b.fill_random(SEED, density)
+            times.append(timed(lambda: b.step(gens), b.sync))
+        share = float((b.settled() >= 0).mean()) if settle else 0.0
+        sums = b.checksums()
+    t = times[1:]
+    return statistics.median(t), min(t), max(t), share, sums
+
+
+def baseline_time(nx, ny, count, gens, reps, density=0.5):
+    """The same for a host loop over `count` Life objects."""
+    lives = [lm.Life(nx, ny) for _ in range(count)]
+    try:
+        def fill():
+            for u, life in enumerate(lives):
+                life.fill_random(SEED + u, density)
+
+        def sync():
+            for life in lives:
+                life.sync()
+
+        def run():
+            for life in lives:
+                life.step(gens)
+
+        times = []
+        for rep in range(reps + 1):
+            fill()
+            times.append(timed(run, sync))
+        paths = {life.last_path() for life in lives}
+        sums = [life.checksum() for life in lives]
+    finally:
+        for life in lives:
+            life.close()
+    t = times[1:]
+    return statistics.median(t), min(t), max(t), sorted(paths), sums
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--gens", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--baseline-count", type=int, default=32, help="Life objects of the baseline's host loop")
+    ap.add_argument("--settle-gens", type=int, default=4096)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--quick", action="store_true", help="the smallest count of every shape only")
+    a = ap.parse_args()
+    out = open(a.out, "w") if a.out else None
+
+    def emit(row):
+        line = json.dumps(row)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    table = []
+    for (nx, ny), counts in ROWS:
+        k = min(a.baseline_count, counts[0])
+        bt, bmin, bmax, paths, bsums = baseline_time(nx, ny, k, a.gens, a.reps)
+        per_universe = bt / k
+        for count in counts[:1] if a.quick else counts:
+            t, tmin, tmax, _, sums = batch_time(nx, ny, count, a.gens, a.reps)
+            if [int(s) for s in sums[:k]] != bsums:
+                raise SystemExit(f"{nx}x{ny}: the batch and the host loop disagree after {a.gens} generations")
+            updates = nx * ny * count * a.gens
+            row = {"shape": [nx, ny], "count": count, "gens": a.gens, "tier": lm.batch_query(nx, ny)[0],
+                   "batch_s": t, "batch_min_s": tmin, "batch_max_s": tmax, "baseline_count": k,
+                   "baseline_s_per_universe": per_universe, "baseline_min_s": bmin / k, "baseline_max_s": bmax / k,
+                   "baseline_paths": paths, "baseline_s_scaled": per_universe * count,
+                   "ratio": per_universe * count / t, "tcups": updates / t / 1e12,
+                   "baseline_tcups": nx * ny * a.gens / per_universe / 1e12}
+            emit(row)
+            table.append(row)
+    # the settle option: reported, not gated
+    nx, ny, count, density = 32, 32, 1024 if a.quick else 16384, 0.35
+    off = batch_time(nx, ny, count, a.settle_gens, a.reps, density, settle=False)
+    on = batch_time(nx, ny, count, a.settle_gens, a.reps, density, settle=True)
+    if list(off[4]) != list(on[4]):
+        raise SystemExit("settle on and off disagree")
+    emit({"settle": True, "shape": [nx, ny], "count": count, "gens": a.settle_gens, "density": density,
+          "off_s": off[0], "off_min_s": off[1], "off_max_s": off[2], "on_s": on[0], "on_min_s": on[1],
+          "on_max_s": on[2], "speedup": off[0] / on[0], "settled_share": on[3]})
+    print("| shape | count | batch ms | host loop ms (scaled) | ratio | Tcell-updates/s |", file=sys.stderr)
+    print("|---|---|---|---|---|---|", file=sys.stderr)
+    for r in table:
+        print(f"| {r['shape'][0]}x{r['shape'][1]} | {r['count']} | {1e3 * r['batch_s']:.3f} | "
+              f"{1e3 * r['baseline_s_scaled']:.1f} | {r['ratio']:.0f} | {r['tcups']:.2f} |", file=sys.stderr)
+
+
+if __name__ == "__main__":
+    main()
