@@ -599,7 +599,9 @@ void life_dev_destroy(life_dev *d);
  *  LIFE_BATCH_TIER_WAVE   1 <= nx <= 128, 1 <= ny <= 64: one universe per
  *                         wave, the whole state in its registers, no barrier
  *                         and no LDS exchange per generation; any rule
- *                         life_dev_set_rule accepts; LIFE_BATCH_OPT_SETTLE.
+ *                         life_dev_set_rule accepts, one for all universes or
+ *                         one each (life_batch_set_rules); LIFE_BATCH_OPT_
+ *                         SETTLE, LIFE_BATCH_OPT_CYCLE.
  *  LIFE_BATCH_TIER_GROUP  every other shape the one-workgroup register kernel
  *                         of the small-grid path takes (at most 2048 cells
  *                         wide, strips of R rows dividing ny, R one of 1 2 3 4
@@ -637,6 +639,24 @@ int life_batch_fill_random(life_batch *b, uint64_t seed, uint32_t thr32);
  * above 8, B0 rules, any rule other than B3/S23 on a group-tier batch. */
 int life_batch_set_rule(life_batch *b, uint32_t birth, uint32_t survive);
 int life_batch_get_rule(life_batch *b, uint32_t *birth, uint32_t *survive);
+/* A rule per universe (wave tier): universes [first, first +
+ * n) take the masks birth[k] / survive[k], the others keep theirs.  The states
+ * and the generation counter are untouched; the settled and cycle flags of the
+ * universes written, and of no others, are cleared.  Ordered on the batch's
+ * stream; the host arrays may be reused on return.  n == 0 is a no-op.
+ * LIFE_EINVAL, with a message naming the first offending index and its rule,
+ * and nothing changed: a bad range (as life_batch_upload), an entry with bits
+ * above 8 or B0, an entry other than B3/S23 on a group-tier batch (which stays
+ * uniform: there the call only clears the flags).
+ * From a call with n > 0 until the next life_batch_set_rule a wave-tier batch
+ * is "mixed", whatever the values: it holds a table of 8 B per universe on the
+ * device (allocated by the first such call, released by life_batch_set_rule),
+ * every universe steps through the table tail of its own masks (B3/S23
+ * included), and life_batch_get_rule returns LIFE_ESTATE (ask life_batch_
+ * get_rules).  life_batch_get_rules always works: on a uniform batch it repeats
+ * the one rule.  Either out pointer may be NULL.  Blocking. */
+int life_batch_set_rules(life_batch *b, int64_t first, int64_t n, const uint32_t *birth, const uint32_t *survive);
+int life_batch_get_rules(life_batch *b, int64_t first, int64_t n, uint32_t *birth, uint32_t *survive);
 /* LIFE_BATCH_OPT_SETTLE (wave tier, value 0 / 1, default 0): while on, a wave
  * compares its universe after each generation of a step call, from the call's
  * second on, with the state two generations earlier.  At the first generation
@@ -645,8 +665,28 @@ int life_batch_get_rule(life_batch *b, uint32_t *birth, uint32_t *survive);
  * and exits: the state it leaves is exactly the state after all n.  A
  * universe already flagged runs n mod 2 generations in later calls.  States
  * are bit-identical with the option on and off.  LIFE_EINVAL: a group-tier
- * batch, any other option or value. */
+ * batch, any other option or value, turning it on while LIFE_BATCH_OPT_CYCLE
+ * is on (two detectors for one wave: pick one).
+ * LIFE_BATCH_OPT_CYCLE (wave tier, value 0 / 1, default 0): cycle detection of
+ * any period by Brent's algorithm, restarted at every step call.  In a call of
+ * n generations from state S_0 at absolute generation G_0: T = S_0, power = 1,
+ * lam = 0; for g = 1 .. n: compute S_g, increment lam; if S_g == T the
+ * universe is cyclic with the exact minimal period lam, recorded with the
+ * absolute generation G_0 + g (life_batch_cycles), and detection stops; else
+ * if lam == power: T = S_g, power *= 2, lam = 0.  The checkpoints fall at g =
+ * 2^k - 1, and a cycle of period p entered after m generations is found at g
+ * = c + p for the first checkpoint c >= m with c + 1 >= p.  After detection
+ * at g the wave runs (n - g) mod p more generations and exits; a universe
+ * already flagged runs n mod p generations in later calls.  States are bit-
+ * identical with the option on and off.  Detection restarts per call: a call
+ * of n generations finds what Brent finds within n, so a long run belongs in
+ * few long calls (a glider on a 32 x 32 torus, period 128, is found by one
+ * step(255) and not by step(100) + step(155)).  life_batch_settled is not
+ * touched by this option.  LIFE_EINVAL: a group-tier batch, a value other
+ * than 0 / 1, turning it on while LIFE_BATCH_OPT_SETTLE is on.
+ * Option number 2 is unassigned and stays LIFE_EINVAL. */
 #define LIFE_BATCH_OPT_SETTLE 1
+#define LIFE_BATCH_OPT_CYCLE 3
 int life_batch_configure(life_batch *b, int option, int value);
 /* All universes advance `generations`.  Asynchronous (one launch); 0 is a
  * no-op; LIFE_EINVAL when negative or above INT32_MAX. */
@@ -659,6 +699,12 @@ int life_batch_census(life_batch *b, int64_t *live, uint64_t *checksum);
  * life_batch_generation) at which LIFE_BATCH_OPT_SETTLE found it settled, -1
  * if it has not.  Blocking. */
 int life_batch_settled(life_batch *b, int64_t *generation);
+/* Per universe, `count` entries each, either may be NULL: the period
+ * LIFE_BATCH_OPT_CYCLE found and the absolute generation it found it at; 0 and
+ * -1 where it has found none.  A universe's pair goes back to 0 / -1 with an
+ * upload or a life_batch_set_rules range that covers it, all of them with
+ * life_batch_fill_random and life_batch_set_rule.  Blocking. */
+int life_batch_cycles(life_batch *b, int64_t *period, int64_t *generation);
 /* Generations stepped since the states were last written as a whole
  * (creation, life_batch_fill_random, an upload of all universes).  Host only. */
 int life_batch_generation(life_batch *b, int64_t *generation);

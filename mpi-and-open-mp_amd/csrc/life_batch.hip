@@ -4,6 +4,9 @@
 // life_batch_kernels.hip.  Every call sets the batch's device and enqueues on
 // its stream; the blocking ones wait for it.
 #include <limits.h>
+#include <stdio.h>
+
+#include <vector>
 
 #include "life_batch_kernels.h"
 #include "life_dev_internal.h"
@@ -24,7 +27,11 @@ struct life_batch {
     uint32_t birth = life::kConwayBirth, survive = life::kConwaySurvive;
     bool table = false;
     life::RuleWords words{};
+    // "mixed" (life_batch_set_rules): (birth, survive) of universe u at rules[2 u]; null on a uniform batch
+    uint32_t *rules = nullptr;
     bool settle = false;
+    bool cycle = false;
+    int64_t *cycles = nullptr;  // period[count], found[count] of LIFE_BATCH_OPT_CYCLE (from its first use)
     int64_t generation = 0;
 };
 
@@ -51,9 +58,40 @@ int range_ok(const life_batch *b, int64_t first, int64_t n, const void *grids, c
     return LIFE_OK;
 }
 
-// settled flags of universes [first, first + n) back to -1
+// settled flags of universes [first, first + n) back to -1, their cycle pairs to 0 / -1
 int clear_settled(life_batch *b, int64_t first, int64_t n) {
-    if (n > 0) HIPCHK(hipMemsetAsync(b->settled + first, 0xFF, sizeof(int64_t) * (size_t)n, b->stream));
+    if (n < 1) return LIFE_OK;
+    HIPCHK(hipMemsetAsync(b->settled + first, 0xFF, sizeof(int64_t) * (size_t)n, b->stream));
+    if (b->cycles) {
+        HIPCHK(hipMemsetAsync(b->cycles + first, 0, sizeof(int64_t) * (size_t)n, b->stream));
+        HIPCHK(hipMemsetAsync(b->cycles + b->count + first, 0xFF, sizeof(int64_t) * (size_t)n, b->stream));
+    }
+    return LIFE_OK;
+}
+
+// bits above 8 and B0, as life_batch_set_rule refuses them; `at` >= 0: an entry of life_batch_set_rules
+int rule_ok(uint32_t birth, uint32_t survive, int64_t at) {
+    char where[48] = "";
+    if (at >= 0) snprintf(where, sizeof where, "life_batch_set_rules: entry %lld: ", (long long)at);
+    if ((birth | survive) & ~life::kRuleMask) {
+        set_err("%srule masks 0x%x / 0x%x: bits above 8", where, birth, survive);
+        return LIFE_EINVAL;
+    }
+    if (birth & 1u) {
+        char name[24];
+        life::rule_format(birth, survive, name);
+        set_err("%srule %s: B0 rules are not supported (padding bits and idle lanes must stay dead)", where, name);
+        return LIFE_EINVAL;
+    }
+    return LIFE_OK;
+}
+
+// the table of a mixed batch is released: the batch is uniform again
+int drop_rules(life_batch *b) {
+    if (!b->rules) return LIFE_OK;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(hipFree(b->rules));
+    b->rules = nullptr;
     return LIFE_OK;
 }
 
@@ -61,6 +99,8 @@ void free_batch(life_batch *b) {
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     if (b->cells) (void)hipFree(b->cells);
     if (b->settled) (void)hipFree(b->settled);
+    if (b->rules) (void)hipFree(b->rules);
+    if (b->cycles) (void)hipFree(b->cycles);
     if (b->census) (void)hipFree(b->census);
     if (b->stage) (void)hipFree(b->stage);
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -171,16 +211,9 @@ int life_batch_fill_random(life_batch *b, uint64_t seed, uint32_t thr32) {
 
 int life_batch_set_rule(life_batch *b, uint32_t birth, uint32_t survive) {
     if (!b) return LIFE_EINVAL;
-    if ((birth | survive) & ~life::kRuleMask) {
-        set_err("rule masks 0x%x / 0x%x: bits above 8", birth, survive);
-        return LIFE_EINVAL;
-    }
+    CHK(rule_ok(birth, survive, -1));
     char name[24];
     life::rule_format(birth, survive, name);
-    if (birth & 1u) {
-        set_err("rule %s: B0 rules are not supported (padding bits and idle lanes must stay dead)", name);
-        return LIFE_EINVAL;
-    }
     const bool conway = birth == life::kConwayBirth && survive == life::kConwaySurvive;
     if (!conway && b->plan.tier != LIFE_BATCH_TIER_WAVE) {
         set_err("rule %s: a group-tier batch (%lld x %lld) runs B3/S23 only (rules are a feature of the wave tier)", name,
@@ -188,6 +221,7 @@ int life_batch_set_rule(life_batch *b, uint32_t birth, uint32_t survive) {
         return LIFE_EINVAL;
     }
     HIPCHK(hipSetDevice(b->device));
+    CHK(drop_rules(b));
     CHK(clear_settled(b, 0, b->count));
     b->birth = birth;
     b->survive = survive;
@@ -198,23 +232,116 @@ int life_batch_set_rule(life_batch *b, uint32_t birth, uint32_t survive) {
 
 int life_batch_get_rule(life_batch *b, uint32_t *birth, uint32_t *survive) {
     if (!b) return LIFE_EINVAL;
+    if (b->rules) {
+        set_err("life_batch_get_rule: the batch holds a rule per universe (life_batch_set_rules): ask "
+                "life_batch_get_rules");
+        return LIFE_ESTATE;
+    }
     if (birth) *birth = b->birth;
     if (survive) *survive = b->survive;
     return LIFE_OK;
 }
 
+int life_batch_set_rules(life_batch *b, int64_t first, int64_t n, const uint32_t *birth, const uint32_t *survive) {
+    if (!b) return LIFE_EINVAL;
+    CHK(range_ok(b, first, n, birth && survive ? (const void *)birth : nullptr, "life_batch_set_rules"));
+    if (n == 0) return LIFE_OK;
+    const bool wave = b->plan.tier == LIFE_BATCH_TIER_WAVE;
+    for (int64_t k = 0; k < n; k++) {
+        CHK(rule_ok(birth[k], survive[k], k));
+        if (!wave && (birth[k] != life::kConwayBirth || survive[k] != life::kConwaySurvive)) {
+            char name[24];
+            life::rule_format(birth[k], survive[k], name);
+            set_err("life_batch_set_rules: entry %lld: rule %s: a group-tier batch (%lld x %lld) runs B3/S23 only "
+                    "(rules are a feature of the wave tier)", (long long)k, name, (long long)b->nx, (long long)b->ny);
+            return LIFE_EINVAL;
+        }
+    }
+    HIPCHK(hipSetDevice(b->device));
+    if (wave) {
+        // the first call lays the whole table down: the uniform rule, then the range
+        const bool fresh = !b->rules;
+        const int64_t lo = fresh ? 0 : first, m = fresh ? b->count : n;
+        std::vector<uint32_t> host((size_t)(2 * m));
+        uint32_t *table = b->rules;
+        if (fresh) {
+            HIPCHK(hipMalloc(&table, 2 * sizeof(uint32_t) * (size_t)b->count));
+            for (int64_t u = 0; u < m; u++) {
+                host[2 * u] = b->birth;
+                host[2 * u + 1] = b->survive;
+            }
+        }
+        for (int64_t k = 0; k < n; k++) {
+            host[2 * (first - lo + k)] = birth[k];
+            host[2 * (first - lo + k) + 1] = survive[k];
+        }
+        // waited for: `host` leaves scope, and a table that did not arrive is not kept
+        hipError_t e = hipMemcpyAsync(table + 2 * lo, host.data(), sizeof(uint32_t) * host.size(),
+                                      hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+        if (e != hipSuccess && fresh) (void)hipFree(table);
+        HIPCHK(e);
+        b->rules = table;
+        return clear_settled(b, first, n);
+    }
+    return clear_settled(b, first, n);
+}
+
+int life_batch_get_rules(life_batch *b, int64_t first, int64_t n, uint32_t *birth, uint32_t *survive) {
+    if (!b) return LIFE_EINVAL;
+    CHK(range_ok(b, first, n, b, "life_batch_get_rules"));
+    if (n == 0) return LIFE_OK;
+    if (!b->rules) {
+        for (int64_t k = 0; k < n; k++) {
+            if (birth) birth[k] = b->birth;
+            if (survive) survive[k] = b->survive;
+        }
+        return LIFE_OK;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    std::vector<uint32_t> host((size_t)(2 * n));
+    HIPCHK(hipMemcpyAsync(host.data(), b->rules + 2 * first, sizeof(uint32_t) * host.size(), hipMemcpyDeviceToHost,
+                          b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int64_t k = 0; k < n; k++) {
+        if (birth) birth[k] = host[2 * k];
+        if (survive) survive[k] = host[2 * k + 1];
+    }
+    return LIFE_OK;
+}
+
 int life_batch_configure(life_batch *b, int option, int value) {
     if (!b) return LIFE_EINVAL;
-    if (option != LIFE_BATCH_OPT_SETTLE || (value != 0 && value != 1)) {
+    // (option 2 is unassigned)
+    if ((option != LIFE_BATCH_OPT_SETTLE && option != LIFE_BATCH_OPT_CYCLE) || (value != 0 && value != 1)) {
         set_err("life_batch_configure: option %d value %d", option, value);
         return LIFE_EINVAL;
     }
+    const bool settle = option == LIFE_BATCH_OPT_SETTLE;
+    const char *name = settle ? "LIFE_BATCH_OPT_SETTLE" : "LIFE_BATCH_OPT_CYCLE";
     if (b->plan.tier != LIFE_BATCH_TIER_WAVE) {
-        set_err("LIFE_BATCH_OPT_SETTLE: a group-tier batch (%lld x %lld) has no settle detection", (long long)b->nx,
-                (long long)b->ny);
+        set_err("%s: a group-tier batch (%lld x %lld) has no %s detection", name, (long long)b->nx, (long long)b->ny,
+                settle ? "settle" : "cycle");
         return LIFE_EINVAL;
     }
-    b->settle = value != 0;
+    if (value && (settle ? b->cycle : b->settle)) {
+        set_err("%s: %s is on (two detectors for one wave: turn that one off first)", name,
+                settle ? "LIFE_BATCH_OPT_CYCLE" : "LIFE_BATCH_OPT_SETTLE");
+        return LIFE_EINVAL;
+    }
+    if (settle) {
+        b->settle = value != 0;
+        return LIFE_OK;
+    }
+    if (value && !b->cycles) {
+        HIPCHK(hipSetDevice(b->device));
+        HIPCHK(hipMalloc(&b->cycles, 2 * sizeof(int64_t) * (size_t)b->count));
+        // the new pairs to 0 / -1 (the settled flags are not this option's)
+        const size_t bytes = sizeof(int64_t) * (size_t)b->count;
+        HIPCHK(hipMemsetAsync(b->cycles, 0, bytes, b->stream));
+        HIPCHK(hipMemsetAsync(b->cycles + b->count, 0xFF, bytes, b->stream));
+    }
+    b->cycle = value != 0;
     return LIFE_OK;
 }
 
@@ -226,7 +353,12 @@ int life_batch_step(life_batch *b, int64_t generations) {
     }
     if (generations == 0) return LIFE_OK;
     HIPCHK(hipSetDevice(b->device));
-    if (b->plan.tier == LIFE_BATCH_TIER_WAVE)
+    if (b->plan.tier == LIFE_BATCH_TIER_WAVE && (b->rules || b->cycle))
+        HIPCHK(life::launch_batch_survey(b->plan, b->nx, b->ny, b->count, b->cells, generations,
+                                         b->table ? &b->words : nullptr, b->rules, b->settle, b->settled, b->cycle,
+                                         b->cycles, b->cycles ? b->cycles + b->count : nullptr, b->generation,
+                                         b->stream));
+    else if (b->plan.tier == LIFE_BATCH_TIER_WAVE)
         HIPCHK(life::launch_batch_wave(b->plan, b->nx, b->ny, b->count, b->cells, generations,
                                        b->table ? &b->words : nullptr, b->settle, b->settled, b->generation,
                                        b->stream));
@@ -257,6 +389,23 @@ int life_batch_settled(life_batch *b, int64_t *generation) {
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipMemcpyAsync(generation, b->settled, sizeof(int64_t) * (size_t)b->count, hipMemcpyDeviceToHost,
                           b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+int life_batch_cycles(life_batch *b, int64_t *period, int64_t *generation) {
+    if (!b) return LIFE_EINVAL;
+    if (!b->cycles) {  // LIFE_BATCH_OPT_CYCLE was never on
+        for (int64_t u = 0; u < b->count; u++) {
+            if (period) period[u] = 0;
+            if (generation) generation[u] = -1;
+        }
+        return LIFE_OK;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    const size_t bytes = sizeof(int64_t) * (size_t)b->count;
+    if (period) HIPCHK(hipMemcpyAsync(period, b->cycles, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (generation) HIPCHK(hipMemcpyAsync(generation, b->cycles + b->count, bytes, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return LIFE_OK;
 }

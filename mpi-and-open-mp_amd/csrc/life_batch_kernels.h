@@ -18,6 +18,16 @@ namespace life {
 // generation before this call; off, `settled` is not touched.
 hipError_t launch_batch_wave(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
                              const RuleWords *rule, bool settle, int64_t *settled, int64_t gen0, hipStream_t s);
+// The survey forms of the wave tier, kernels of their own
+// beside the uniform ones above.  rules non-null: a rule per universe, (birth,
+// survive) pairs of 32-bit masks, universe u's at rules[2 u]; the wave expands
+// its own into the table tail (`rule` is then ignored).  cycle: the detection
+// of LIFE_BATCH_OPT_CYCLE with period[u] / found[u] the universe's pair (0 /
+// -1, or the period and the generation it was found at); never with settle.
+// One of rules and cycle must be set: the rest is launch_batch_wave's.
+hipError_t launch_batch_survey(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
+                               const RuleWords *rule, const uint32_t *rules, bool settle, int64_t *settled, bool cycle,
+                               int64_t *period, int64_t *found, int64_t gen0, hipStream_t s);
 // Group tier (B3/S23): one workgroup per universe.
 hipError_t launch_batch_group(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
                               int64_t gens, hipStream_t s);

@@ -62,14 +62,19 @@ struct BWArgs {
     int64_t count, gen0;
     int32_t nx, ny, gens;
     RuleWords rule;
+    const uint2 *rules;        // per-universe forms: (birth, survive) of universe u
+    int64_t *period, *found;   // cycle detection: 0 / -1, or the period and the generation it was found at
 };
 
-template <int W, class RP, bool SETTLE>
-__global__ __launch_bounds__(64 * kBatchWaves) void batch_wave_kernel(BWArgs a) {
-    const int lane = (int)(threadIdx.x & 63u);
-    const int64_t u = (int64_t)blockIdx.x * kBatchWaves + (int64_t)(threadIdx.x >> 6);
-    if (u >= a.count) return;  // the whole wave
-    const RP rp = make_rule<RP>(a.rule);
+// what a wave watches its universe for (LIFE_BATCH_OPT_SETTLE, LIFE_BATCH_OPT_CYCLE)
+enum Detector { kNoDetector = 0, kSettle = 1, kCycle = 2 };
+
+// The whole life of a wave that owns universe u: load, a.gens generations under
+// rp (fewer when the detector lets it leave early), store.  Shared by every
+// wave-tier kernel.
+template <int W, int DET, class RP>
+__device__ __forceinline__ void wave_body(const BWArgs &a, const int64_t u, const int lane, const RP &rp) {
+    constexpr bool SETTLE = DET == kSettle, CYCLE = DET == kCycle;
     const int ny = a.ny;
     const bool active = lane < ny;
     const int up = !active ? lane : lane == 0 ? ny - 1 : lane - 1;
@@ -93,7 +98,19 @@ __global__ __launch_bounds__(64 * kBatchWaves) void batch_wave_kernel(BWArgs a) 
 #pragma unroll
         for (int j = 0; j < W; ++j) p1[j] = p2[j] = v[j];
     }
-    for (int g = 1; g <= gens; ++g) {
+    // Brent, restarted per call: T the checkpoint, lam generations since it, the
+    // next one when lam reaches power (all wave-uniform)
+    uint32_t T[CYCLE ? W : 1];
+    uint32_t power = 1, lam = 0;
+    if (CYCLE) {
+        // (the same for every lane: tell the compiler so, and the loops below branch on scalars)
+        const uint32_t known = __builtin_amdgcn_readfirstlane((uint32_t)a.period[u]);
+        detect = known == 0u;
+        if (!detect) gens = (int)((uint32_t)gens % known);  // found in an earlier call
+#pragma unroll
+        for (int j = 0; j < W; ++j) T[j] = v[j];
+    }
+    auto generation = [&]() {
         uint32_t s0[W], s1[W];
 #pragma unroll
         for (int j = 0; j < W; ++j) {
@@ -110,6 +127,39 @@ __global__ __launch_bounds__(64 * kBatchWaves) void batch_wave_kernel(BWArgs a) 
             v[j] = rp(a0, a1, s0[j], s1[j], d0, d1, v[j]);
         }
         v[W - 1] &= xw.keep;
+    };
+    if (CYCLE) {
+        // The detecting generations, then the rest without: what is recorded is
+        // written between the two loops, so neither holds a memory access.
+        int rest = gens, g = 1;
+        if (detect) {
+            for (; g <= gens; ++g) {
+                generation();
+                ++lam;
+                uint32_t diff = 0;
+#pragma unroll
+                for (int j = 0; j < W; ++j) diff |= v[j] ^ T[j];
+                if (__builtin_amdgcn_ballot_w64(diff != 0u) == 0ull) break;  // S_g == T: the minimal period is lam
+                if (lam == power) {
+#pragma unroll
+                    for (int j = 0; j < W; ++j) T[j] = v[j];
+                    power <<= 1;
+                    lam = 0;
+                }
+            }
+            rest = 0;
+            if (g <= gens) {
+                if (lane == 0) {
+                    a.period[u] = (int64_t)lam;
+                    a.found[u] = a.gen0 + g;
+                }
+                rest = (int)((uint32_t)(gens - g) % lam);
+            }
+        }
+        for (g = 0; g < rest; ++g) generation();
+    }
+    for (int g = 1; !CYCLE && g <= gens; ++g) {
+        generation();
         if (SETTLE && detect) {
             if (g >= 2) {
                 uint32_t diff = 0;
@@ -133,12 +183,76 @@ __global__ __launch_bounds__(64 * kBatchWaves) void batch_wave_kernel(BWArgs a) 
     for (int j = 0; j < W; ++j) row[j] = v[j];
 }
 
+// The uniform forms without cycle detection: one rule for the launch.
+template <int W, class RP, bool SETTLE>
+__global__ __launch_bounds__(64 * kBatchWaves) void batch_wave_kernel(BWArgs a) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t u = (int64_t)blockIdx.x * kBatchWaves + (int64_t)(threadIdx.x >> 6);
+    if (u >= a.count) return;  // the whole wave
+    const RP rp = make_rule<RP>(a.rule);
+    wave_body<W, SETTLE ? kSettle : kNoDetector>(a, u, lane, rp);
+}
+
 template <int W, class RP>
 hipError_t launch_wave(const BWArgs &a, bool settle, unsigned blocks, hipStream_t s) {
     if (settle)
         batch_wave_kernel<W, RP, true><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
     else
         batch_wave_kernel<W, RP, false><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+// The survey forms: cycle detection under a uniform rule, and a
+// rule per universe under any detector.  A per-universe wave reads its two
+// masks once, before the generation loop, and expands them into the ten
+// leaves of TableRule by life::rule_leaf -- the host's own definition -- so a
+// B3/S23 universe of a mixed batch runs the table too.
+enum SurveyRule { kSurveyConway = 0, kSurveyTable = 1, kSurveyPerUniverse = 2 };
+
+// TableRule of universe u's own masks
+__device__ __forceinline__ TableRule universe_rule(const uint2 *rules, int64_t u) {
+    const uint2 m = rules[u];
+    RuleWords w;
+#pragma unroll
+    for (int q = 0; q < 10; ++q) {
+        const RuleLeaf leaf = rule_leaf(m.x, m.y, q / 5, q % 5);
+        w.a[q / 5][q % 5] = leaf.a;
+        w.b[q / 5][q % 5] = leaf.b;
+    }
+    return TableRule(w);
+}
+
+template <int W, int RULE, int DET>
+__global__ __launch_bounds__(64 * kBatchWaves) void batch_survey_kernel(BWArgs a) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t u = (int64_t)blockIdx.x * kBatchWaves + (int64_t)(threadIdx.x >> 6);
+    if (u >= a.count) return;  // the whole wave
+    if (RULE == kSurveyConway)
+        wave_body<W, DET>(a, u, lane, ConwayRule{});
+    else if (RULE == kSurveyTable)
+        wave_body<W, DET>(a, u, lane, TableRule(a.rule));
+    else
+        wave_body<W, DET>(a, u, lane, universe_rule(a.rules, u));
+}
+
+template <int W>
+hipError_t launch_survey(const BWArgs &a, int rule, int det, unsigned blocks, hipStream_t s) {
+#define LIFE_BS(R, D) batch_survey_kernel<W, R, D><<<blocks, 64 * kBatchWaves, 0, s>>>(a)
+    if (rule == kSurveyPerUniverse) {
+        if (det == kCycle)
+            LIFE_BS(kSurveyPerUniverse, kCycle);
+        else if (det == kSettle)
+            LIFE_BS(kSurveyPerUniverse, kSettle);
+        else
+            LIFE_BS(kSurveyPerUniverse, kNoDetector);
+    } else if (det != kCycle) {
+        return hipErrorInvalidValue;  // the uniform forms without cycle detection are batch_wave_kernel's
+    } else if (rule == kSurveyTable) {
+        LIFE_BS(kSurveyTable, kCycle);
+    } else {
+        LIFE_BS(kSurveyConway, kCycle);
+    }
+#undef LIFE_BS
     return hipGetLastError();
 }
 
@@ -332,6 +446,36 @@ hipError_t launch_batch_wave(const BatchPlan &p, int64_t nx, int64_t ny, int64_t
     case N: return rule ? launch_wave<N, TableRule>(a, settle, blocks, s) : launch_wave<N, ConwayRule>(a, settle, blocks, s);
         LIFE_BW(1) LIFE_BW(2) LIFE_BW(3) LIFE_BW(4)
 #undef LIFE_BW
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_batch_survey(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
+                               const RuleWords *rule, const uint32_t *rules, bool settle, int64_t *settled, bool cycle,
+                               int64_t *period, int64_t *found, int64_t gen0, hipStream_t s) {
+    if (p.tier != LIFE_BATCH_TIER_WAVE || gens < 1 || gens > INT32_MAX || (settle && !settled) || (settle && cycle) ||
+        (cycle && (!period || !found)) || (!rules && !cycle) || !grid_ok((count + kBatchWaves - 1) / kBatchWaves))
+        return hipErrorInvalidValue;
+    BWArgs a{};
+    a.cells = cells;
+    a.settled = settled;
+    a.count = count;
+    a.gen0 = gen0;
+    a.nx = (int32_t)nx;
+    a.ny = (int32_t)ny;
+    a.gens = (int32_t)gens;
+    if (rule) a.rule = *rule;
+    a.rules = reinterpret_cast<const uint2 *>(rules);
+    a.period = period;
+    a.found = found;
+    const int r = rules ? kSurveyPerUniverse : rule ? kSurveyTable : kSurveyConway;
+    const int det = cycle ? kCycle : settle ? kSettle : kNoDetector;
+    const unsigned blocks = wave_blocks(count);
+    switch (p.words) {
+    case 1: return launch_survey<1>(a, r, det, blocks, s);
+    case 2: return launch_survey<2>(a, r, det, blocks, s);
+    case 3: return launch_survey<3>(a, r, det, blocks, s);
+    case 4: return launch_survey<4>(a, r, det, blocks, s);
     default: return hipErrorInvalidValue;
     }
 }

@@ -131,6 +131,22 @@ struct RuleWords {
     uint32_t a[2][5], b[2][5];  // [alive][S]
 };
 RuleWords rule_words(uint32_t birth, uint32_t survive);
+// The one definition of a leaf, for rule_words and for the batch kernels that
+// expand a universe's own masks on the device (life_batch_kernels.hip).
+#ifdef __HIP__
+#define LIFE_HOST_DEVICE __host__ __device__
+#else
+#define LIFE_HOST_DEVICE
+#endif
+struct RuleLeaf { uint32_t a, b; };
+LIFE_HOST_DEVICE inline RuleLeaf rule_leaf(uint32_t birth, uint32_t survive, int alive, int s) {
+    const uint32_t mask = alive ? survive : birth;
+    // next state of a cell whose 3 x 3 block holds n9 live cells; n8 = n9 - alive outside 0 .. 8 cannot occur
+    const int n8 = 2 * s - alive;
+    const uint32_t t0 = n8 >= 0 && n8 <= 8 && ((mask >> n8) & 1u) ? 0xFFFFFFFFu : 0u;
+    const uint32_t t1 = n8 + 1 <= 8 && ((mask >> (n8 + 1)) & 1u) ? 0xFFFFFFFFu : 0u;
+    return RuleLeaf{t0 ^ t1, t0};
+}
 // The text forms: B36/S23 (either letter case) and Golly's 23/3 (S/B);
 // digits 0-8 in any order, repeats and empty lists allowed.  false: not a
 // rulestring.  rule_format writes the canonical B.../S... with ascending digits

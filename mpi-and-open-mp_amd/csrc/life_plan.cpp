@@ -376,17 +376,12 @@ const char *life_dev_strerror(int err) { return life_strerror(err); }
 // ---- Life-like rules (life_host.h)
 life::RuleWords life::rule_words(uint32_t birth, uint32_t survive) {
     RuleWords w;
-    for (int alive = 0; alive < 2; alive++) {
-        auto t = [&](int n9) -> uint32_t {  // next state of a cell whose 3 x 3 block holds n9 live cells
-            const int n8 = n9 - alive;
-            if (n8 < 0 || n8 > 8) return 0u;  // cannot occur
-            return (((alive ? survive : birth) >> n8) & 1u) ? 0xFFFFFFFFu : 0u;
-        };
+    for (int alive = 0; alive < 2; alive++)
         for (int s = 0; s < 5; s++) {
-            w.b[alive][s] = t(2 * s);
-            w.a[alive][s] = t(2 * s) ^ t(2 * s + 1);
+            const RuleLeaf leaf = rule_leaf(birth, survive, alive, s);
+            w.a[alive][s] = leaf.a;
+            w.b[alive][s] = leaf.b;
         }
-    }
     return w;
 }
 

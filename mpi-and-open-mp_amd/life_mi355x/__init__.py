@@ -82,10 +82,12 @@ ABI_SYMBOLS = (
     "life_batch_query", "life_batch_create", "life_batch_destroy", "life_batch_upload", "life_batch_gather",
     "life_batch_fill_random", "life_batch_set_rule", "life_batch_get_rule", "life_batch_configure",
     "life_batch_step", "life_batch_census", "life_batch_settled", "life_batch_generation", "life_batch_sync",
+    "life_batch_set_rules", "life_batch_get_rules", "life_batch_cycles",
 )
 BATCH_TIER_WAVE, BATCH_TIER_GROUP = 1, 2  # LIFE_BATCH_TIER_*
 BATCH_TIERS = {BATCH_TIER_WAVE: "wave", BATCH_TIER_GROUP: "group"}
 BATCH_OPT_SETTLE = 1  # LIFE_BATCH_OPT_SETTLE
+BATCH_OPT_CYCLE = 3  # LIFE_BATCH_OPT_CYCLE (2 is unassigned)
 PATHS = {0: "none", 1: "onegen", 2: "tiles", 3: "flow", 5: "small", 6: "skip"}
 
 
@@ -216,6 +218,10 @@ def _lib():
             L.life_batch_settled.argtypes = [vp, P(i64)]
             L.life_batch_generation.argtypes = [vp, P(i64)]
             L.life_batch_sync.argtypes = [vp]
+        if hasattr(L, "life_batch_set_rules"):  # absent from builds that predate per-universe rules
+            L.life_batch_set_rules.argtypes = [vp, i64, i64, P(u32), P(u32)]
+            L.life_batch_get_rules.argtypes = [vp, i64, i64, P(u32), P(u32)]
+            L.life_batch_cycles.argtypes = [vp, P(i64), P(i64)]
         L.life_tune.argtypes = [i32, i32, i32]
         L.life_tune_temporal.argtypes = [i32, i32]
         L.life_measure_copy.argtypes = [i32, i64, i32, P(ctypes.c_double)]
@@ -663,10 +669,14 @@ class LifeBatch:
     Every call is ordered on the batch's one stream: ``step`` returns at once,
     and a following ``gather`` / ``live_counts`` / ``checksums`` / ``settled``
     waits for it.  ``rule``: None (B3/S23), a rulestring or a (birth, survive)
-    pair (wave tier only).  ``settle``: stop a universe early once it repeats
-    with period 1 or 2 (LIFE_BATCH_OPT_SETTLE; wave tier only)."""
+    pair (wave tier only).  ``rules``: one such rule per universe
+    (:meth:`set_rules`; wave tier only).  ``settle``: stop a universe early once
+    it repeats with period 1 or 2 (LIFE_BATCH_OPT_SETTLE; wave tier only).
+    ``cycle``: find cycles of any period instead (LIFE_BATCH_OPT_CYCLE,
+    :meth:`cycles`; wave tier only, not together with ``settle``)."""
 
-    def __init__(self, nx: int, ny: int, count: int, device: int = 0, rule=None, settle: bool = False):
+    def __init__(self, nx: int, ny: int, count: int, device: int = 0, rule=None, settle: bool = False, rules=None,
+                 cycle: bool = False):
         self.nx, self.ny, self.count = int(nx), int(ny), int(count)
         self._h = ctypes.c_void_p()
         _check(_lib().life_batch_create(self.nx, self.ny, self.count, int(device), ctypes.byref(self._h)),
@@ -674,8 +684,12 @@ class LifeBatch:
         self.tier = batch_query(self.nx, self.ny)[0]
         if rule is not None:
             self.set_rule(rule)
+        if rules is not None:
+            self.set_rules(rules)
         if settle:
             self.configure(BATCH_OPT_SETTLE, 1)
+        if cycle:
+            self.configure(BATCH_OPT_CYCLE, 1)
 
     def configure(self, option: int, value: int) -> None:
         _check(_lib().life_batch_configure(self._h, int(option), int(value)), "life_batch_configure")
@@ -690,9 +704,42 @@ class LifeBatch:
 
     @property
     def rule(self) -> str:
+        """The one rule of a uniform batch; LifeError (LIFE_ESTATE) once
+        :meth:`set_rules` gave the universes rules of their own (see ``rules``)."""
         b, s = ctypes.c_uint32(), ctypes.c_uint32()
         _check(_lib().life_batch_get_rule(self._h, ctypes.byref(b), ctypes.byref(s)), "life_batch_get_rule")
         return format_rule(b.value, s.value)
+
+    def set_rules(self, rules, first: int = 0) -> None:
+        """life_batch_set_rules: universes [first, first + len(rules)) take
+        ``rules``, a sequence of rulestrings or (birth, survive) pairs; the
+        others keep theirs.  Clears the settled and cycle flags of those
+        universes.  The batch steps a rule per universe until :meth:`set_rule`."""
+        masks = [_rule_masks(r) for r in rules]
+        for birth, survive in masks:
+            if not (0 <= birth < 2**32 and 0 <= survive < 2**32):
+                raise ValueError(f"rule masks {birth}, {survive} are not 32-bit")
+        birth = np.array([m[0] for m in masks], dtype=np.uint32)
+        survive = np.array([m[1] for m in masks], dtype=np.uint32)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        _check(_lib().life_batch_set_rules(self._h, int(first), len(masks), birth.ctypes.data_as(u32p),
+                                           survive.ctypes.data_as(u32p)), "life_batch_set_rules")
+
+    def rule_masks(self, first: int = 0, n: int | None = None):
+        """(birth, survive) uint32 arrays of universes [first, first + n)
+        (life_batch_get_rules; n None: all from `first` on)."""
+        first = int(first)
+        n = self.count - first if n is None else int(n)
+        birth, survive = np.zeros(max(n, 0), dtype=np.uint32), np.zeros(max(n, 0), dtype=np.uint32)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        _check(_lib().life_batch_get_rules(self._h, first, n, birth.ctypes.data_as(u32p),
+                                           survive.ctypes.data_as(u32p)), "life_batch_get_rules")
+        return birth, survive
+
+    @property
+    def rules(self) -> list:
+        """The canonical rulestring of every universe."""
+        return [format_rule(int(b), int(s)) for b, s in zip(*self.rule_masks())]
 
     @property
     def generation(self) -> int:
@@ -750,6 +797,16 @@ class LifeBatch:
         _check(_lib().life_batch_settled(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
                "life_batch_settled")
         return out
+
+    def cycles(self):
+        """(period, generation) int64 arrays of LIFE_BATCH_OPT_CYCLE: per
+        universe the exact period it was found to repeat with and the generation
+        it was found at; 0 and -1 where none was found."""
+        period, found = np.zeros(self.count, dtype=np.int64), np.zeros(self.count, dtype=np.int64)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        _check(_lib().life_batch_cycles(self._h, period.ctypes.data_as(i64p), found.ctypes.data_as(i64p)),
+               "life_batch_cycles")
+        return period, found
 
     def sync(self) -> None:
         _check(_lib().life_batch_sync(self._h), "life_batch_sync")

@@ -11,7 +11,16 @@ the same shape; before timing, the first universes' checksums of both paths
 are compared after the warm-up run.  One JSON line per row on stdout (and in
 --out), a markdown table on stderr.
 
+The survey lines, reported and not gated.  Per-universe
+rules: 262144 universes of 64 x 64, 50 % soups, step(1024), HighLife for every
+universe through set_rules against the same batch under the uniform
+set_rule("B36/S23") -- the uniform table kernel is the yardstick, the
+difference is the price of a rule per universe.  Cycle detection: the settle
+line's batch (16384 soups of 32 x 32 at 35 %, step(4096)) with detection off,
+settle on and cycle on, and the share of universes each detector found.
+
     python scripts/batch_bench.py --out profiles/batch/batch_bench.jsonl
+    python scripts/batch_bench.py --only survey --out profiles/batch/survey_bench.jsonl
 """
 import argparse
 import json
@@ -38,14 +47,17 @@ def timed(fn, sync):
     return time.perf_counter() - t0
 
 
-def batch_time(nx, ny, count, gens, reps, density=0.5, settle=False):
-    """(median s, min s, max s, settled share) of LifeBatch.step(gens)."""
-    with lm.LifeBatch(nx, ny, count, settle=settle) as b:
+def batch_time(nx, ny, count, gens, reps, density=0.5, settle=False, rule=None, rules=None, cycle=False):
+    """(median s, min s, max s, share of universes the detector found, checksums)
+    of LifeBatch.step(gens); rules: one rule for every universe, through set_rules."""
+    with lm.LifeBatch(nx, ny, count, settle=settle, rule=rule, cycle=cycle) as b:
+        if rules is not None:
+            b.set_rules([lm.parse_rule(rules)] * count)
         times = []
         for rep in range(reps + 1):  # the first is the warm-up
             b.fill_random(SEED, density)
             times.append(timed(lambda: b.step(gens), b.sync))
-        share = float((b.settled() >= 0).mean()) if settle else 0.0
+        share = float((b.settled() >= 0).mean()) if settle else float((b.cycles()[0] > 0).mean()) if cycle else 0.0
         sums = b.checksums()
     t = times[1:]
     return statistics.median(t), min(t), max(t), share, sums
@@ -88,6 +100,8 @@ def main():
     ap.add_argument("--settle-gens", type=int, default=4096)
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="the smallest count of every shape only")
+    ap.add_argument("--only", choices=("all", "table", "settle", "survey"), default="all",
+                    help="the shape table, the settle line or the survey lines alone")
     a = ap.parse_args()
     out = open(a.out, "w") if a.out else None
 
@@ -99,7 +113,7 @@ def main():
             out.flush()
 
     table = []
-    for (nx, ny), counts in ROWS:
+    for (nx, ny), counts in ROWS if a.only in ("all", "table") else []:
         k = min(a.baseline_count, counts[0])
         bt, bmin, bmax, paths, bsums = baseline_time(nx, ny, k, a.gens, a.reps)
         per_universe = bt / k
@@ -118,13 +132,36 @@ def main():
             table.append(row)
     # the settle option: reported, not gated
     nx, ny, count, density = 32, 32, 1024 if a.quick else 16384, 0.35
-    off = batch_time(nx, ny, count, a.settle_gens, a.reps, density, settle=False)
-    on = batch_time(nx, ny, count, a.settle_gens, a.reps, density, settle=True)
-    if list(off[4]) != list(on[4]):
-        raise SystemExit("settle on and off disagree")
-    emit({"settle": True, "shape": [nx, ny], "count": count, "gens": a.settle_gens, "density": density,
-          "off_s": off[0], "off_min_s": off[1], "off_max_s": off[2], "on_s": on[0], "on_min_s": on[1],
-          "on_max_s": on[2], "speedup": off[0] / on[0], "settled_share": on[3]})
+    if a.only in ("all", "settle", "survey"):
+        off = batch_time(nx, ny, count, a.settle_gens, a.reps, density, settle=False)
+        on = batch_time(nx, ny, count, a.settle_gens, a.reps, density, settle=True)
+        if list(off[4]) != list(on[4]):
+            raise SystemExit("settle on and off disagree")
+    if a.only in ("all", "settle"):
+        emit({"settle": True, "shape": [nx, ny], "count": count, "gens": a.settle_gens, "density": density,
+              "off_s": off[0], "off_min_s": off[1], "off_max_s": off[2], "on_s": on[0], "on_min_s": on[1],
+              "on_max_s": on[2], "speedup": off[0] / on[0], "settled_share": on[3]})
+    if a.only in ("all", "survey"):
+        # cycle detection beside settle, on the settle line's batch
+        cyc = batch_time(nx, ny, count, a.settle_gens, a.reps, density, cycle=True)
+        if list(off[4]) != list(cyc[4]):
+            raise SystemExit("cycle detection on and off disagree")
+        emit({"cycle": True, "shape": [nx, ny], "count": count, "gens": a.settle_gens, "density": density,
+              "off_s": off[0], "off_min_s": off[1], "off_max_s": off[2], "settle_s": on[0], "settle_min_s": on[1],
+              "settle_max_s": on[2], "settled_share": on[3], "cycle_s": cyc[0], "cycle_min_s": cyc[1],
+              "cycle_max_s": cyc[2], "cycle_share": cyc[3], "settle_speedup": off[0] / on[0],
+              "cycle_speedup": off[0] / cyc[0]})
+        # the price of a rule per universe: the uniform table kernel is the yardstick
+        nx, ny, count, rule = 64, 64, 1024 if a.quick else 262144, "B36/S23"
+        uni = batch_time(nx, ny, count, a.gens, a.reps, rule=rule)
+        per = batch_time(nx, ny, count, a.gens, a.reps, rules=rule)
+        if list(uni[4]) != list(per[4]):
+            raise SystemExit("uniform and per-universe HighLife disagree")
+        emit({"per_universe_rules": True, "shape": [nx, ny], "count": count, "gens": a.gens, "rule": rule,
+              "uniform_s": uni[0], "uniform_min_s": uni[1], "uniform_max_s": uni[2], "per_universe_s": per[0],
+              "per_universe_min_s": per[1], "per_universe_max_s": per[2], "per_universe_over_uniform": per[0] / uni[0],
+              "uniform_tcups": nx * ny * count * a.gens / uni[0] / 1e12,
+              "per_universe_tcups": nx * ny * count * a.gens / per[0] / 1e12})
     print("| shape | count | batch ms | host loop ms (scaled) | ratio | Tcell-updates/s |", file=sys.stderr)
     print("|---|---|---|---|---|---|", file=sys.stderr)
     for r in table:
