@@ -477,6 +477,26 @@ int life_dev_set_timing(life_dev *d, int on);
  * pipelined passes overlap in time); LIFE_OPT_SKIP_DEAD keeps acting, and a
  * pass of a recording call leaves the activity maps valid. */
 #define LIFE_OPT_POPULATION 13
+/* LIFE_OPT_RULE7 (default LIFE_RULE7 from the environment, else 3; 0..3, any
+ * other value LIFE_EINVAL): which forms of the B3/S23 bit tiles compute the
+ * rule in 7 bit operations per dword instead of 8 (20 instead of 22 VALU
+ * instructions per pair row and generation: the column sums kept as parity
+ * and not-all-equal) -- LIFE_RULE7_TILES: the per-launch tiles
+ * in every launch form (whole block, ring / interior, deep-halo passes,
+ * banded columns, half-height tail, pipelined regions), LIFE_RULE7_FLOW: the
+ * dataflow tiles (LIFE_OPT_FLOW).  Both arms are separate kernels of the same
+ * tile code and give bit-identical results; 0 runs the 8-gate kernels
+ * everywhere (the A/B arm).  Accepted on every device; without effect on the
+ * byte encoding, under a rule other than B3/S23, and on the census
+ * (LIFE_OPT_POPULATION), skip-dead, one-generation and small-grid kernels,
+ * which have one arm.  life_dev_kernel_work keeps counting 22 operations per
+ * pair row for both arms ("22-op equivalents"), so rates of the two compare.
+ * life_dev_last_rule_arm: the forms (the same bits) of which at least one launch
+ * of the LAST life_dev_step call ran the 7-gate arm; 0 when none did. */
+#define LIFE_OPT_RULE7 14
+#define LIFE_RULE7_TILES 1
+#define LIFE_RULE7_FLOW 2
+int life_dev_last_rule_arm(life_dev *d);
 int life_dev_configure(life_dev *d, int option, int value);
 /* The population trace of the LAST life_dev_step call.  Blocking: waits for
  * the device.  *generations (may be NULL) = the generations that call

@@ -15,8 +15,9 @@
 // A row's horizontal 3-sums are a 2-bit number per cell (full adder of the
 // cell and its two neighbours); three rows' sums give n9 = u0 + 2*S, and the
 // B3/S23 rule of life_cart.c:202-208 / life2d.c:117-123 becomes 8
-// v_bitop3_b32 (a 3-gate tail is impossible: exhaustive search,
-// profiles/r03/rule_search.txt).
+// v_bitop3_b32 (a 3-gate tail is impossible over the full adder's (parity,
+// majority) column sums: exhaustive search, profiles/r03/rule_search.txt; it
+// exists over (parity, not-all-equal): ConwayRule7 below, 7 per dword).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -133,6 +134,28 @@ struct ConwayRule {
     __device__ __forceinline__ uint32_t operator()(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0,
                                                    uint32_t c1, uint32_t alive) const {
         return BitEnc::rule1(a0, a1, b0, b1, c0, c1, alive);
+    }
+};
+
+// B3/S23 in 7 v_bitop3 per dword instead of rule1's 8 (LIFE_OPT_RULE7; the
+// tstep_bit7 / tflow7 kernels).  The column sums W0 = a0 + b0 + c0 and W1 =
+// a1 + b1 + c1 cost two gates each under any injective 2-bit encoding; kept
+// as (parity, not all equal) rather than (parity, majority) the tail takes
+// three gates, not four (scripts/rule_search7.c over all nine encoding pairs,
+// profiles/rule7/rule_search7.txt; none takes two).  Of the circuits found
+// this one reads `alive` in its last gate only, which kept the window
+// registers' live ranges and so the compiler's permute schedule as rule1's
+// (tests/test_isa_rule7.py).  Immediates: life_host.h, shared with the host
+// evaluator life::conway7_host.
+struct ConwayRule7 {
+    static constexpr bool kTable = false;
+    __device__ __forceinline__ uint32_t operator()(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0,
+                                                   uint32_t c1, uint32_t alive) const {
+        const uint32_t p = b3<kR7Par>(a0, b0, c0), n = b3<kR7Nae>(a0, b0, c0);
+        const uint32_t x = b3<kR7Par>(a1, b1, c1), y = b3<kR7Nae>(a1, b1, c1);
+        const uint32_t g1 = b3<kR7G1>(p, n, y);
+        const uint32_t g2 = b3<kR7G2>(n, x, g1);
+        return b3<kR7Out>(p, alive, g2);
     }
 };
 

@@ -69,6 +69,10 @@ static const int kEnvPipeline = [] {
     const int v = life::env::read(life::env::kPipeline);
     return v == 2 ? life::env::kPipeline.dflt : v;
 }();
+// LIFE_RULE7 (0..3) sets LIFE_OPT_RULE7's default at load time: the forms
+// (LIFE_RULE7_TILES | LIFE_RULE7_FLOW) whose B3/S23 bit tiles run the 7-gate
+// arm (life_kernels.hip tstep_bit7_kernel / tflow7_kernel)
+static const int kEnvRule7 = life::env::read(life::env::kRule7);
 static int default_block_gens(int kernel) {
     return kEnvBlockGens ? kEnvBlockGens : (kernel == LIFE_KERNEL_BIT ? 12 : 32);
 }
@@ -201,6 +205,7 @@ life_dev *new_dev(int64_t nx, int64_t ny, int dims0, int dims1, int world, int k
     d->deep = kEnvDeepHalo;
     d->flow = kEnvFlow;
     d->pipe = kEnvPipeline;
+    d->rule7 = kEnvRule7;
     return d;
 }
 
@@ -232,7 +237,7 @@ void tail_prewarm(const life_dev *d) {
         bool seen = false;  // identical blocks share their plans (cached by shape)
         for (size_t j = 0; j < i; ++j)
             seen |= d->shards[j].lay.w == d->shards[i].lay.w && d->shards[j].lay.h == d->shards[i].lay.h;
-        if (!seen) life::prewarm_tail_plans(d->shards[i].lay, max_pass_gens(d), part(d, 1), d->table);
+        if (!seen) life::prewarm_tail_plans(d->shards[i].lay, max_pass_gens(d), part(d, 1), d->table, rule7_tiles(d));
     }
 }
 
@@ -538,6 +543,12 @@ int life_dev_configure(life_dev *d, int option, int value) {
     case LIFE_OPT_PIPELINE:
         if (value < 0 || value == 2 || value > life::kPipeMaxRegions) return LIFE_EINVAL;
         d->pipe = value;
+        return LIFE_OK;
+    case LIFE_OPT_RULE7:
+        // accepted on every device; it acts on the B3/S23 bit tiles (rule7_tiles / rule7_flow)
+        if (value < 0 || value > (LIFE_RULE7_TILES | LIFE_RULE7_FLOW)) return LIFE_EINVAL;
+        d->rule7 = value;
+        tail_prewarm(d);  // the tail plans count the slots of the kernel that will run
         return LIFE_OK;
     case LIFE_OPT_FLOW_CHUNK:
         if (value < 0) return LIFE_EINVAL;

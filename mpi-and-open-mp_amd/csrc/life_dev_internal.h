@@ -153,6 +153,9 @@ struct life_dev {
     uint32_t birth = life::kConwayBirth, survive = life::kConwaySurvive;
     bool table = false;
     life::RuleWords words{};
+    // LIFE_OPT_RULE7: the forms whose B3/S23 bit tiles run the 7-gate arm (LIFE_RULE7_TILES | LIFE_RULE7_FLOW;
+    // creation: LIFE_RULE7), and the forms that did in the last step call (life_dev_last_rule_arm)
+    int rule7 = 0, last_rule7 = 0;
     int pipe = 0;  // LIFE_OPT_PIPELINE: 0 off, 1 automatic, R >= 3 regions whenever a plan exists (creation: LIFE_PIPELINE)
     // the current step call's pipelined passes (life_step.hip pipelined_pass): R = 0, none; the plan
     // and the pass count of the current run of passes of m generations (a new m: a new run)
@@ -197,6 +200,14 @@ inline bool part(const life_dev *d, int a) { return d->dims[a] > 1 || ((d->loop 
 inline bool self_wrap_x(const life_dev *d) { return !(d->loop & 1) && life::self_wrap_x(d->shards[0].lay, d->dims[0]); }
 // The table-rule kernels' words, null under B3/S23 (launch_step / launch_tstep).
 inline const life::RuleWords *rule_of(const life_dev *d) { return d->table ? &d->words : nullptr; }
+// The per-launch / dataflow tiles of this device run their 7-gate arm (LIFE_OPT_RULE7): B3/S23 bit tiles
+// only (launch_tstep ignores it under a table rule; the census and skip-dead tiles have one arm).
+inline bool rule7_tiles(const life_dev *d) {
+    return (d->rule7 & LIFE_RULE7_TILES) && d->kernel == LIFE_KERNEL_BIT && !d->table && !d->population;
+}
+inline bool rule7_flow(const life_dev *d) {
+    return (d->rule7 & LIFE_RULE7_FLOW) && d->kernel == LIFE_KERNEL_BIT && !d->table;
+}
 inline life::Wrap wrap_of(const life_dev *d) { return life::Wrap{!part(d, 0) && !self_wrap_x(d), !part(d, 1)}; }
 inline bool temporal(const life_dev *d) { return d->shards[0].lay.generations_per_exchange > 1; }
 // Deep halo applies (generation_block): bit tiles, a partitioned axis, no

@@ -71,6 +71,9 @@ constexpr IntKnob kFlow{"LIFE_FLOW", 3, 0, 3};
 constexpr FlagKnob kDeepHalo{"LIFE_DEEP_HALO", 1};
 // default of LIFE_OPT_PIPELINE: 0 off, 1 automatic, 3..16 that many row regions per pass (profiles/pipeline)
 constexpr IntKnob kPipeline{"LIFE_PIPELINE", 1, 0, 16};
+// default of LIFE_OPT_RULE7: bit 0 the per-launch bit tiles, bit 1 the dataflow tiles run B3/S23 in 7 gates
+// per dword (ConwayRule7) instead of 8; 0: the 8-gate kernels everywhere (A/B knob; profiles/rule7)
+constexpr IntKnob kRule7{"LIFE_RULE7", 3, 0, 3};
 // timed launches: 0 one event pair per call, 1 per launch, 2 stamped by the dispatch, 3 no events (read by tests)
 constexpr IntKnob kTimingMode{"LIFE_TIMING_MODE", 0, 0, 3};
 // 1: allocations filled with 0xA5 instead of zeros; read at every life_dev_create* (tests set it in-process)

@@ -147,6 +147,26 @@ LIFE_HOST_DEVICE inline RuleLeaf rule_leaf(uint32_t birth, uint32_t survive, int
     const uint32_t t1 = n8 + 1 <= 8 && ((mask >> (n8 + 1)) & 1u) ? 0xFFFFFFFFu : 0u;
     return RuleLeaf{t0 ^ t1, t0};
 }
+// B3/S23 in 7 gates per dword (ConwayRule7, life_bitops.h; the search: scripts/rule_search7.c,
+// profiles/rule7/rule_search7.txt).  The column sums W0 = a0 + b0 + c0 and W1 = a1 + b1 + c1 are
+// kept as (parity, not all equal) instead of the full adder's (parity, majority): p, n of W0 and
+// x, y of W1, then g1 = b3<kR7G1>(p, n, y), g2 = b3<kR7G2>(n, x, g1), out = b3<kR7Out>(p, alive, g2).
+// Immediates as b3<IMM>: IMM = f(0xF0, 0xCC, 0xAA), the first operand most significant.
+constexpr uint32_t kR7Par = 0x96;  // a ^ b ^ c: W odd
+constexpr uint32_t kR7Nae = 0x7E;  // not all equal: W is 1 or 2
+constexpr uint32_t kR7G1 = 0x56;   // c ^ (a | b)
+constexpr uint32_t kR7G2 = 0x42;   // (a ^ c) & ~(a ^ b)
+constexpr uint32_t kR7Out = 0xA8;  // c & (a | b)
+// v_bitop3_b32 on the host: bit i of the result is bit (a_i, b_i, c_i) of imm
+inline uint32_t bitop3_host(uint32_t imm, uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r = 0;
+    for (int k = 0; k < 8; k++)
+        if ((imm >> k) & 1u) r |= ((k & 4) ? a : ~a) & ((k & 2) ? b : ~b) & ((k & 1) ? c : ~c);
+    return r;
+}
+// ConwayRule7 word for word on the host (life_plan.cpp): 32 cells per call, checked against the
+// definition over all 128 inputs by tests/test_rule7_host.py
+uint32_t conway7_host(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0, uint32_t c1, uint32_t alive);
 // The text forms: B36/S23 (either letter case) and Golly's 23/3 (S/B);
 // digits 0-8 in any order, repeats and empty lists allowed.  false: not a
 // rulestring.  rule_format writes the canonical B.../S... with ascending digits

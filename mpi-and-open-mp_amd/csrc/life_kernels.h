@@ -100,19 +100,22 @@ bool flow_ok(const life_layout &L, int m);
 // last column; the queue also holds no-op items that pad the last group of
 // banded rows unless work_only)
 int64_t flow_items_per_pass(const life_layout &L, int m, bool work_only = false);
-int flow_slots(const life_layout &L);  // resident workgroups of L's dataflow kernel on this device
+// resident workgroups of L's dataflow kernel on this device (rule7: of its 7-gate arm, tflow7_kernel)
+int flow_slots(const life_layout &L, bool rule7 = false);
 // resident workgroups of L's per-launch tile kernel on this device (rule: of its table-rule instance)
-int tile_slots(const life_layout &L, bool rule = false);
+// (rule7: of the 7-gate arm, tstep_bit7_kernel)
+int tile_slots(const life_layout &L, bool rule = false, bool rule7 = false);
 // ev0 / ev1 (optional): events stamped with the kernel dispatch's own start
 // and end (hipExtLaunchKernel) -- no event packets between launches.
 // One empty launch of the dataflow instance launch_tflow(L, m, flow) would use
 // (and its occupancy query): the first launch of a kernel in a process costs
 // ~140 us, which a device pays here at creation instead of inside its first
 // dataflow step call.  `head`: the caller's scratch (2 words).
-hipError_t prewarm_tflow(const life_layout &L, int m, int flow, unsigned int *head, hipStream_t s);
+hipError_t prewarm_tflow(const life_layout &L, int m, int flow, unsigned int *head, hipStream_t s,
+                         bool rule7 = false);
 hipError_t launch_tflow(const life_layout &L, const uint8_t *in, uint8_t *out, int m, int64_t passes,
                         unsigned int *head, unsigned int *done, Wrap wrap, int flow, hipStream_t s,
-                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, bool rule7 = false);
 // Deep-halo passes (bit tiles, partitioned axes): the pass also advances the
 // apron cells that stay valid for the next pass -- y rows [-y, 0) and
 // [h, h + y) (the tile grid then spans h + 2y rows from owned row -y; the
@@ -134,7 +137,11 @@ hipError_t launch_tstep(const life_layout &L, const uint8_t *in, uint8_t *out, c
                         int m, Wrap wrap, hipStream_t s,
                         double *valu_lane_ops = nullptr, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
                         Extend ext = Extend{}, int64_t concurrent = 0, const RuleWords *rule = nullptr,
-                        unsigned long long *pop = nullptr);
+                        unsigned long long *pop = nullptr, bool rule7 = false);
+// `rule7` (here, in launch_tflow and prewarm_tflow; LIFE_OPT_RULE7): the B3/S23
+// bit tiles run their 7-gate arm (ConwayRule7, life_bitops.h: 20 VALU per pair
+// row instead of 22) -- the kernels of a launch without `rule` and `pop`; the
+// table-rule, census, skip-dead and byte tiles have one arm and ignore it.
 // Census instances of the bit tiles (LIFE_OPT_POPULATION): with `pop` (here
 // and in launch_tskip; bit shards of whole pairs, w % 64 == 0) every tile of
 // the launch also adds the live cells it owns after each of the m generations
@@ -170,7 +177,7 @@ hipError_t launch_tskip(const life_layout &L, const uint8_t *in, uint8_t *out, i
 // ext_y: also every deep-halo extension 0 .. K - m), so that a step call
 // does not pay the planner's search (~50 us per new shape) before its first
 // launch.
-void prewarm_tail_plans(const life_layout &L, int mmax, bool ext_y, bool rule = false);
+void prewarm_tail_plans(const life_layout &L, int mmax, bool ext_y, bool rule = false, bool rule7 = false);
 // The layout a deep-halo pass tiles: h + 2 ext.y rows starting ext.y rows
 // into the top apron.
 life_layout extended_layout(const life_layout &L, const Extend &ext);

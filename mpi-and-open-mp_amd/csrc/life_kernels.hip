@@ -1068,6 +1068,21 @@ __device__ __forceinline__ void tstep_bit_body(const TArgs &a, XchB<NW> &xch, co
     wg_trace(1);
 }
 
+// The same tiles with B3/S23 in 7 gates per dword (ConwayRule7, life_bitops.h;
+// LIFE_OPT_RULE7): per pair row 2 v_alignbit + 2 full adders (4) + 2 x 7 = 20
+// VALU against tstep_bit_kernel's 22, under the same launch bounds (80 VGPRs
+// at 3 tiles per CU) and over the same items; tests/test_isa_rule7.py pins
+// the count and the schedule.
+// A kernel of its own name: tstep_bit_kernel stays in the build, its text and
+// code untouched, as the A/B arm (LIFE_RULE7=0) and the instance
+// tests/test_isa.py reads.  The model behind kernel_work() keeps counting 22
+// per pair row for both arms (tstep_valu_per_tile_lane).
+template <int R, bool WRAPX, bool WRAPY, int NW>
+__global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tstep_bit7_kernel(TArgs a) {
+    __shared__ XchB<NW> xch;
+    tstep_bit_body<R, WRAPX, WRAPY, NW>(a, xch, ConwayRule7{});
+}
+
 // The same tiles under a table rule (life_dev_set_rule): the tail is 25
 // v_bitop3 per dword instead of 12 and its 20 uniform words live in VGPRs,
 // so the instance is compiled for 2 tiles per CU (4 waves per SIMD, at most
@@ -1423,6 +1438,129 @@ __global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tflow_kernel(FArgs f)
     }
 }
 
+// tflow_kernel again under a rule policy, for the 7-gate arm below (a twin for
+// the reason given at tstep_bit_body: tflow_kernel keeps its own text and so
+// its code, the A/B arm and the instance tests/test_isa.py reads).  Queue,
+// dependency wait and hand-off are tflow_kernel's, line for line.
+template <int R, bool WRAPX, bool WRAPY, int FLOW, int NW, bool BAND, class RP>
+__device__ __forceinline__ void tflow_body(const FArgs &f, XchB<NW> &xch, unsigned int &item_sh, const RP &rule) {
+    const TArgs &a = f.t;
+    const int64_t tiles = f.ntx * f.nty;
+    const int lane = threadIdx.x & 63;
+    unsigned int *prev_flag = nullptr;
+    unsigned int prev_val = 0;
+    int prev_n = 0;
+    int traced = 0;
+    wg_trace(0);
+    for (;;) {
+        // ONE thread-0 region per iteration (see tflow_kernel)
+        if (!BAND && threadIdx.x == 0) {
+            if (prev_flag) {
+                if (FLOW == 2) {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+                __hip_atomic_store(prev_flag, prev_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            item_sh = atomicAdd(f.head, 1u);
+        }
+        if (BAND && threadIdx.x < 64) {
+            if (prev_n > 0) {
+                if (FLOW == 2) {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+                if (lane < prev_n)
+                    __hip_atomic_store(prev_flag + (int64_t)lane * f.ntx, prev_val, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (lane == 0) item_sh = atomicAdd(f.head, 1u);
+        }
+        __syncthreads();
+        const uint32_t item = __builtin_amdgcn_readfirstlane(item_sh);
+        if ((int64_t)item >= f.items) return;  // the whole workgroup leaves
+        if (LIFE_WG_TRACE && traced < 4) wg_trace(1 + 3 * traced);
+        const uint32_t ntx = (uint32_t)f.ntx, nty = (uint32_t)f.nty;
+        uint32_t p;
+        int64_t tx, ty;
+        int nb = 1;
+        if (!BAND) {
+            p = item / (uint32_t)tiles;
+            const uint32_t k = item - p * (uint32_t)tiles, kr = k / ntx;
+            tx = k - kr * ntx;
+            ty = (kr + p) % nty;
+        } else {
+            p = item / (uint32_t)f.per_pass;
+            const uint32_t k = item - p * (uint32_t)f.per_pass;
+            const uint32_t nfull = ntx - 1, G1 = nfull * (uint32_t)f.B + 1u;
+            const uint32_t g = k / G1, off = k - g * G1;
+            const int64_t ty0 = (int64_t)((g + p) % (uint32_t)f.ngroups) * f.B;
+            if (off < nfull * (uint32_t)f.B) {
+                tx = off % nfull;
+                ty = ty0 + off / nfull;
+            } else {
+                tx = a.btx1 - 1;
+                ty = ty0;
+                nb = (int)(f.nty - ty0 < f.B ? f.nty - ty0 : f.B);
+            }
+            if (ty >= f.nty) {  // a padding item of the last group
+                prev_n = 0;
+                prev_flag = nullptr;
+                __syncthreads();
+                continue;
+            }
+        }
+        if (p > 0 && threadIdx.x < 64) {
+            bool ok = true;
+            const unsigned int *flag = nullptr;
+            if (lane < 3 * (nb + 4)) {
+                const int64_t dy = lane / 3 - 2, dx = lane % 3 - 1;
+                int64_t yy = (ty + dy) % f.nty, xx = (tx + dx) % f.ntx;
+                if (yy < 0) yy += f.nty;
+                if (xx < 0) xx += f.ntx;
+                flag = f.done + yy * f.ntx + xx;
+            }
+            for (uint32_t spin = 0;; ++spin) {  // bounded, as tflow_kernel's
+                if (flag)
+                    ok = __hip_atomic_load(const_cast<unsigned int *>(flag), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT) >= p;
+                if (__all(ok)) break;
+                if (spin == (1u << 20)) {
+                    if (lane == 0) atomicMax(f.head + 1, item + 1);
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(2);
+            }
+            if (FLOW == 2) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
+        __syncthreads();
+        if (LIFE_WG_TRACE && traced < 4) wg_trace(2 + 3 * traced);
+        const uint8_t *in = (p & 1) ? a.out : a.in;
+        uint8_t *out = const_cast<uint8_t *>((p & 1) ? a.in : a.out);
+        if (BAND && tx == a.btx1 - 1)
+            tile_body_bit<R, WRAPX, WRAPY, FLOW, NW, true>(a, in, out, tx, ty, xch, a.bgsh[0], nb, 0, -1, a.borg[0],
+                                                           a.bown[0], rule);
+        else
+            tile_body_bit<R, WRAPX, WRAPY, FLOW, NW>(a, in, out, tx, ty, xch, 6, 1, 0, -1, 0, 62, rule);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have left
+        __syncthreads();
+        if (LIFE_WG_TRACE && traced < 4) wg_trace(3 + 3 * traced++);
+        prev_flag = f.done + ty * f.ntx + tx;
+        prev_val = p + 1;
+        prev_n = nb;
+    }
+}
+// the dataflow tiles with B3/S23 in 7 gates per dword (ConwayRule7; LIFE_OPT_RULE7, bit 1)
+template <int R, bool WRAPX, bool WRAPY, int FLOW, int NW, bool BAND = false>
+__global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tflow7_kernel(FArgs f) {
+    __shared__ XchB<NW> xch;
+    __shared__ unsigned int item_sh;
+    tflow_body<R, WRAPX, WRAPY, FLOW, NW, BAND>(f, xch, item_sh, ConwayRule7{});
+}
+
 // Natural 32-cell word j of a bit-encoded row (bit k = cell 32j + k) from
 // the pair layout and back: the even / odd halves are 16-bit halves of the
 // pair's E / O dwords.  Small-grid kernels work in natural words inside the
@@ -1759,6 +1897,11 @@ int tile_waves(bool) { return kStackWaves; }
 // Census instances (pop): kPopValuPerPairRow more per pair row and generation
 // (the two v_bcnt; the wave's reduction and the ownership test are per
 // generation, not per row, and not modelled).
+// The 7-gate arm (LIFE_OPT_RULE7: 20 per pair row) is priced at the same 22:
+// the model counts the work of the 8-gate formulation for both arms, so the
+// booked lane-ops and the roofline fractions built on them are "22-op
+// equivalents" that compare across the arms (a faster arm shows a higher
+// fraction); what really issues is pinned by tests/test_isa_rule7.py.
 double tstep_valu_per_tile_lane(int m, bool byte, bool rule, bool pop) {
     if (byte) return (double)kStackWaves * (double)temporal_rows(false) * (12.0 * (double)m + 35.0);
     return (double)tile_waves(true) * (double)temporal_rows(true) *
@@ -1886,7 +2029,13 @@ const void *byte_k(Wrap wrap) {
 }
 
 template <int R, int NW>
-const void *bit_fn(Wrap wrap) {
+const void *bit_fn(Wrap wrap, bool rule7) {
+    if (rule7) {  // the 7-gate arm (tstep_bit7_kernel)
+        if (wrap.x && wrap.y) return (const void *)tstep_bit7_kernel<R, true, true, NW>;
+        if (wrap.x) return (const void *)tstep_bit7_kernel<R, true, false, NW>;
+        if (wrap.y) return (const void *)tstep_bit7_kernel<R, false, true, NW>;
+        return (const void *)tstep_bit7_kernel<R, false, false, NW>;
+    }
     if (wrap.x && wrap.y) return (const void *)tstep_bit_kernel<R, true, true, NW>;
     if (wrap.x) return (const void *)tstep_bit_kernel<R, true, false, NW>;
     if (wrap.y) return (const void *)tstep_bit_kernel<R, false, true, NW>;
@@ -1895,15 +2044,15 @@ const void *bit_fn(Wrap wrap) {
 
 // the bit tile shape's instances: per-launch tiles and the occupancy probe
 #define LIFE_BIT_SHAPES(X) X(24, 8) X(16, 8)
-const void *bit_k(Wrap wrap) {
+const void *bit_k(Wrap wrap, bool rule7) {
     const int R = temporal_rows(true), NW = tile_waves(true);
 #define LIFE_BIT_CASE(r, nw) \
-    if (R == r && NW == nw) return bit_fn<r, nw>(wrap);
+    if (R == r && NW == nw) return bit_fn<r, nw>(wrap, rule7);
     LIFE_BIT_SHAPES(LIFE_BIT_CASE)
 #undef LIFE_BIT_CASE
     return nullptr;
 }
-const void *tstep_bit_fn() { return bit_k(Wrap{true, true}); }
+const void *tstep_bit_fn(bool rule7) { return bit_k(Wrap{true, true}, rule7); }
 
 // the same shapes under a table rule (trule_bit_kernel)
 template <int R, int NW>
@@ -2020,15 +2169,15 @@ static int slots_of(const void *fn, int threads) {
         return 0;
     return cus * per;
 }
-// the bit tiles of the current shape (cached per shape)
-static int tstep_bit_slots() {
-    static int cached = 0, key = -1;
+// the bit tiles of the current shape, of either arm (cached per shape and arm)
+static int tstep_bit_slots(bool rule7) {
+    static int cached[2] = {0, 0}, key[2] = {-1, -1};
     const int k = temporal_rows(true) * 64 + tile_waves(true);
-    if (k != key) {
-        cached = slots_of(tstep_bit_fn(), 64 * tile_waves(true));
-        key = k;
+    if (k != key[rule7]) {
+        cached[rule7] = slots_of(tstep_bit_fn(rule7), 64 * tile_waves(true));
+        key[rule7] = k;
     }
-    return cached;
+    return cached[rule7];
 }
 // the table-rule tiles of the current shape: 2 per CU, not 3
 static int trule_bit_slots() {
@@ -2041,8 +2190,8 @@ static int trule_bit_slots() {
     return cached;
 }
 
-int tile_slots(const life_layout &L, bool rule) {
-    if (is_bit(L)) return rule ? trule_bit_slots() : tstep_bit_slots();
+int tile_slots(const life_layout &L, bool rule, bool rule7) {
+    if (is_bit(L)) return rule ? trule_bit_slots() : tstep_bit_slots(rule7);
     static int cached = 0, key = -1;
     const int k = temporal_rows(false);
     if (k != key) {
@@ -2077,15 +2226,15 @@ life_layout extended_layout(const life_layout &L, const Extend &ext) {
 // ty1) of tile_geom(L, m), beside `pre` items of another launch dispatched
 // just before it (launch_tstep; cached by life::tail_plan).
 static TailPlan tail_plan_for(const life_layout &L, const TileGeom &g, int m, int64_t tx0, int64_t tx1, int64_t ty0,
-                              int64_t ty1, int64_t pre, bool rule) {
+                              int64_t ty1, int64_t pre, bool rule, bool rule7) {
     const int64_t T2 = (int64_t)tile_waves(true) * (temporal_rows(true) / 2) - 2 * (int64_t)tile_ghost(L, m);
     const int64_t yend = std::min(ty1 * g.rows, L.h);
     const BandRows b = region_bands(g, tx1);
     return tail_plan(tx1 - tx0 - (b.n > 0 ? 1 : 0), b, ty0, ty1, yend, g.rows, T2,
-                     rule ? trule_bit_slots() : tstep_bit_slots(), tail_split_mode(), kTailC, pre);
+                     rule ? trule_bit_slots() : tstep_bit_slots(rule7), tail_split_mode(), kTailC, pre);
 }
 
-void prewarm_tail_plans(const life_layout &L, int mmax, bool ext_y, bool rule) {
+void prewarm_tail_plans(const life_layout &L, int mmax, bool ext_y, bool rule, bool rule7) {
     if (!is_bit(L) || L.generations_per_exchange < 2 || tail_split_mode() == 0) return;
     const int K = L.generations_per_exchange;
     for (int m = 1; m <= std::min(mmax, K); ++m)
@@ -2094,7 +2243,7 @@ void prewarm_tail_plans(const life_layout &L, int mmax, bool ext_y, bool rule) {
             x.y = e;
             const life_layout V = extended_layout(L, x);
             const TileGeom g = tile_geom(V, m);
-            if (g.rows >= 1) (void)tail_plan_for(V, g, m, 0, g.ntx, 0, g.nty, 0, rule);
+            if (g.rows >= 1) (void)tail_plan_for(V, g, m, 0, g.ntx, 0, g.nty, 0, rule, rule7);
         }
 }
 
@@ -2112,7 +2261,7 @@ static void set_bands(TArgs &a, const TileGeom &g) {
 
 hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out, const TileRegion *r, int nreg,
                         int m, Wrap wrap, hipStream_t s, double *valu_lane_ops, hipEvent_t ev0, hipEvent_t ev1,
-                        Extend ext, int64_t concurrent, const RuleWords *rule, unsigned long long *pop) {
+                        Extend ext, int64_t concurrent, const RuleWords *rule, unsigned long long *pop, bool rule7) {
     const int K = Lin.generations_per_exchange;
     const bool bit = is_bit(Lin);
     if (rule && !bit) return hipErrorInvalidValue;  // no quiet B3/S23 in its place
@@ -2168,7 +2317,7 @@ hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out,
         const int64_t tx0 = a.tx0[0], tx1 = a.tx1[0], ty0 = a.ty0[0], ty1 = a.ty1[0];
         const int64_t yend = std::min(ty1 * g.rows, L.h);
         const BandRows bands = region_bands(g, tx1);
-        const TailPlan p = tail_plan_for(L, g, m, tx0, tx1, ty0, ty1, concurrent, rule != nullptr);
+        const TailPlan p = tail_plan_for(L, g, m, tx0, tx1, ty0, ty1, concurrent, rule != nullptr, rule7);
         if (p.F < ty1 && p.F >= ty0) {
             a.ty1[0] = p.F;
             a.first[1] = region_items(g, TileRegion{tx0, tx1, ty0, p.F});
@@ -2206,7 +2355,8 @@ hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out,
         RTArgs ra{a, *rule};
         return launch_fn(rfn, (unsigned)items, 64u * (unsigned)tile_waves(true), &ra, s, ev0, ev1);
     }
-    const void *fn = bit                      ? bit_k(wrap)
+    // (B3/S23 without a census, here: the only tiles with a 7-gate arm)
+    const void *fn = bit                      ? bit_k(wrap, rule7)
                      : byte_one_ghost(L, m) ? byte_fn<48, 1>(wrap)
                      : K == 16              ? byte_k<16>(wrap)
                                             : byte_k<32>(wrap);
@@ -2307,9 +2457,19 @@ namespace {
 // and hand-off form.
 // (LIFE_FLOW_BANDS=0: full-width tiles in the last column; A/B knob)
 bool flow_bands_enabled() { static const bool on = env::read(env::kFlowBands) != 0; return on; }
-const void *flow_kernel_of(const life_layout &L, int flow, bool band = false) {
+const void *flow_kernel_of(const life_layout &L, int flow, bool band = false, bool rule7 = false) {
     if (!is_bit(L)) return nullptr;
     const int R = temporal_rows(true), NW = tile_waves(true);
+#define LIFE_BIT_CASE(r, nw)                                                                     \
+    if (rule7 && R == r && NW == nw) {                                                           \
+        if (band)                                                                                \
+            return flow == 2 ? (const void *)tflow7_kernel<r, true, true, 2, nw, true>           \
+                             : (const void *)tflow7_kernel<r, true, true, 1, nw, true>;          \
+        return flow == 2 ? (const void *)tflow7_kernel<r, true, true, 2, nw>                     \
+                         : (const void *)tflow7_kernel<r, true, true, 1, nw>;                    \
+    }
+    LIFE_BIT_SHAPES(LIFE_BIT_CASE)
+#undef LIFE_BIT_CASE
 #define LIFE_BIT_CASE(r, nw)                                                                     \
     if (R == r && NW == nw) {                                                                    \
         if (band)                                                                                \
@@ -2345,20 +2505,20 @@ bool flow_ok(const life_layout &L, int m) {
     return g.rows >= tile_ghost(L, m);
 }
 
-int flow_slots(const life_layout &L) {
-    static int cached = 0, key = -1;
+int flow_slots(const life_layout &L, bool rule7) {
+    static int cached[2] = {0, 0}, key[2] = {-1, -1};
     const int k = is_bit(L) ? temporal_rows(true) * 64 + tile_waves(true) : -2;
-    if (k != key) {
-        cached = slots_of(flow_kernel_of(L, 1), 64 * tile_waves(is_bit(L)));
-        key = k;
+    if (k != key[rule7]) {
+        cached[rule7] = slots_of(flow_kernel_of(L, 1, false, rule7), 64 * tile_waves(is_bit(L)));
+        key[rule7] = k;
     }
-    return cached;
+    return cached[rule7];
 }
 
-hipError_t prewarm_tflow(const life_layout &L, int m, int flow, unsigned int *head, hipStream_t s) {
+hipError_t prewarm_tflow(const life_layout &L, int m, int flow, unsigned int *head, hipStream_t s, bool rule7) {
     const TileGeom g = flow_geom(L, m);
-    const void *fn = flow_kernel_of(L, flow, flow_band(g));
-    if (!fn || !flow_ok(L, m) || flow_slots(L) <= 0) return hipErrorInvalidValue;  // (caches the slot count)
+    const void *fn = flow_kernel_of(L, flow, flow_band(g), rule7);
+    if (!fn || !flow_ok(L, m) || flow_slots(L, rule7) <= 0) return hipErrorInvalidValue;  // (caches the slot count)
     FArgs f{};  // no items: the one workgroup pulls item 0 and leaves
     f.head = head;
     const hipError_t e = hipMemsetAsync(head, 0, sizeof(unsigned int), s);
@@ -2368,8 +2528,8 @@ hipError_t prewarm_tflow(const life_layout &L, int m, int flow, unsigned int *he
 
 hipError_t launch_tflow(const life_layout &L, const uint8_t *in, uint8_t *out, int m, int64_t passes,
                         unsigned int *head, unsigned int *done, Wrap wrap, int flow, hipStream_t s, hipEvent_t ev0,
-                        hipEvent_t ev1) {
-    const void *fn = flow_kernel_of(L, flow);
+                        hipEvent_t ev1, bool rule7) {
+    const void *fn = flow_kernel_of(L, flow, false, rule7);
     if (!fn || !wrap.x || !wrap.y || m < 1 || m > 32 || m > L.generations_per_exchange || passes < 1 ||
         !flow_ok(L, m))
         return hipErrorInvalidValue;
@@ -2384,7 +2544,7 @@ hipError_t launch_tflow(const life_layout &L, const uint8_t *in, uint8_t *out, i
     f.t.ya = L.yapron;
     f.t.m = m;
     const bool band = flow_band(g);
-    if (band) fn = flow_kernel_of(L, flow, true);
+    if (band) fn = flow_kernel_of(L, flow, true, rule7);
     TileGeom gb = g;
     if (!band) gb.nband = 0, gb.bcol = -1;
     set_bands(f.t, gb);
@@ -2399,7 +2559,7 @@ hipError_t launch_tflow(const life_layout &L, const uint8_t *in, uint8_t *out, i
     hipError_t e = hipMemsetAsync(head, 0, sizeof(unsigned int), s);  // the error word is the caller's
     if (e == hipSuccess) e = hipMemsetAsync(done, 0, sizeof(unsigned int) * (size_t)(g.ntx * g.nty), s);
     if (e != hipSuccess) return e;
-    const int n = flow_slots(L);  // resident workgroups
+    const int n = flow_slots(L, rule7);  // resident workgroups
     if (n <= 0) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)std::min<int64_t>(f.items, n);
     // every workgroup pulls one item past the last: the 32-bit head must not wrap

@@ -385,6 +385,15 @@ life::RuleWords life::rule_words(uint32_t birth, uint32_t survive) {
     return w;
 }
 
+uint32_t life::conway7_host(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0, uint32_t c1,
+                            uint32_t alive) {
+    const uint32_t p = bitop3_host(kR7Par, a0, b0, c0), n = bitop3_host(kR7Nae, a0, b0, c0);
+    const uint32_t x = bitop3_host(kR7Par, a1, b1, c1), y = bitop3_host(kR7Nae, a1, b1, c1);
+    const uint32_t g1 = bitop3_host(kR7G1, p, n, y);
+    const uint32_t g2 = bitop3_host(kR7G2, n, x, g1);
+    return bitop3_host(kR7Out, p, alive, g2);
+}
+
 namespace {
 // digits 0-8 up to `end` (a '/' or the NUL) into a mask
 bool rule_digits(const char *&p, char end, uint32_t *mask) {

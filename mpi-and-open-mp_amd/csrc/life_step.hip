@@ -108,7 +108,8 @@ int launch_tiles(life_dev *d, Shard &s, const life::TileRegion *r, int nreg, int
     CHK(bracket_begin(d, s, timed, 1, kExtModeExt | kExtModeCall, false, st, &b));
     double valu = 0.0;
     HIPCHK(life::launch_tstep(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], r, nreg, m, wrap_of(d), st, &valu, b.ext_a,
-                              b.ext_b, xt, concurrent, rule_of(d), pop_of(d, s)));
+                              b.ext_b, xt, concurrent, rule_of(d), pop_of(d, s), rule7_tiles(d)));
+    if (rule7_tiles(d)) d->last_rule7 |= LIFE_RULE7_TILES;
     CHK(bracket_end(b, st));
     if (b.t) {  // (no timer counts it -- span-only timing, LIFE_TIMING_MODE=3: no booking)
         const life::TileGeom g = life::tile_geom(life::extended_layout(s.lay, xt), m);
@@ -204,7 +205,8 @@ int pipelined_pass(life_dev *d, Shard &s, int m) {
         const life::TileRegion reg{0, g.ntx, P.ty[r], P.ty[r + 1]};
         double v = 0.0;
         HIPCHK(life::launch_tstep(s.lay, s.buf[s.cur], s.buf[s.cur ^ 1], &reg, 1, m, wrap_of(d), q, &v, nullptr,
-                                  nullptr, life::Extend{}, -1, rule_of(d)));
+                                  nullptr, life::Extend{}, -1, rule_of(d), nullptr, rule7_tiles(d)));
+        if (rule7_tiles(d)) d->last_rule7 |= LIFE_RULE7_TILES;
         valu += v;
         if (P.record[j]) HIPCHK(hipEventRecord(s.ev_pipe[i % kPipeRing], q));
     }
@@ -413,7 +415,7 @@ int generation_block(life_dev *d, const life::PassPlan &p) {
             int64_t ring_items = 0;
             for (int k = 0; k < n; k++) ring_items += life::region_items(g, ring[k]);
             const int64_t items = life::region_items(g, inner) + ring_items;
-            *halo_side = carry_on_halo_side(items, life::tile_slots(s.lay, d->table)) ? 1 : 0;
+            *halo_side = carry_on_halo_side(items, life::tile_slots(s.lay, d->table, rule7_tiles(d))) ? 1 : 0;
             // LIFE_INTERIOR_TAIL=1: the interior's launch-tail plan counts the
             // ring's tiles, dispatched just before it, as holding their slots
             // (16384 x 32768's 584 interior tiles beside 249 ring tiles are one
@@ -547,7 +549,8 @@ int flow_form(const life_dev *d, int *m_out) {
     // against 73.7-75.2 T, profiles/r06/d; under one round the dataflow
     // form overlaps the passes in the idle slots)
     if (d->flow == 3) {
-        const double rounds = (double)life::flow_items_per_pass(L, m) / (double)std::max(life::flow_slots(L), 1);
+        const double rounds =
+            (double)life::flow_items_per_pass(L, m) / (double)std::max(life::flow_slots(L, rule7_flow(d)), 1);
         return rounds < kFlowAutoRounds && !(rounds >= 1.0 && rounds < 1.5) ? 1 : 0;
     }
     return d->flow;
@@ -587,7 +590,8 @@ int64_t flow_passes(const life_dev *d, int64_t generations, int *form, int *m, i
     // past the last item: split the passes so that items + grid stays below
     // 2^31 per launch (life::flow_chunk_passes), flipping the buffer parity
     // per chunk.
-    *per = life::flow_chunk_passes(life::flow_items_per_pass(L, *m), life::flow_slots(L), d->flow_chunk);
+    *per = life::flow_chunk_passes(life::flow_items_per_pass(L, *m), life::flow_slots(L, rule7_flow(d)),
+                                   d->flow_chunk);
     return *per < 1 ? 0 : passes;  // a grid too large for one pass per launch: per-launch tiles
 }
 
@@ -610,7 +614,8 @@ int step_flow(life_dev *d, int64_t generations, int64_t *done) {
         Bracket b;
         CHK(bracket_begin(d, s, true, (int)n, kExtModeExt, false, s.stream, &b));  // stats: mean per pass
         HIPCHK(life::launch_tflow(L, s.buf[s.cur], s.buf[s.cur ^ 1], m, n, s.flow, s.flow + 2, wrap_of(d),
-                                  form, s.stream, b.ext_a, b.ext_b));
+                                  form, s.stream, b.ext_a, b.ext_b, rule7_flow(d)));
+        if (rule7_flow(d)) d->last_rule7 |= LIFE_RULE7_FLOW;
         CHK(bracket_end(b, s.stream));
         // work is booked only beside a timer that counts the launch (as
         // launch_tiles / launch_region: LIFE_TIMING_MODE=3 and span-only
@@ -793,7 +798,7 @@ int pipe_regions(const life_dev *d, int64_t generations) {
     int R = d->pipe;
     if (R == 1) {
         R = kPipeAutoRegions;
-        const int slots = life::tile_slots(L, d->table);
+        const int slots = life::tile_slots(L, d->table, rule7_tiles(d));
         if (passes < kPipeAutoPasses || slots < 1 ||
             (double)life::region_items(g, life::TileRegion{0, g.ntx, 0, g.nty}) < kPipeAutoRounds * R * slots)
             return 0;
@@ -894,7 +899,7 @@ int life::rt::flow_prewarm(life_dev *d) {
     Shard &s = d->shards[0];
     CHK(flow_scratch(s, m));
     HIPCHK(hipSetDevice(s.device));
-    HIPCHK(life::prewarm_tflow(s.lay, m, form, s.flow, s.stream));
+    HIPCHK(life::prewarm_tflow(s.lay, m, form, s.flow, s.stream, rule7_flow(d)));
     HIPCHK(hipStreamSynchronize(s.stream));
     return LIFE_OK;
 }
@@ -912,12 +917,15 @@ int life_dev_step(life_dev *d, int64_t generations) {
     d->call_pass_max_ms = 0.0;
     d->call_spans = false;
     d->act_passes = d->act_total = 0;
+    d->last_rule7 = 0;
     const int rc = step_call(d, generations);
     d->call_host_ms = ms_since(t0);
     return rc;
 }
 
 int life_dev_last_path(life_dev *d) { return d ? d->last_path : LIFE_EINVAL; }
+
+int life_dev_last_rule_arm(life_dev *d) { return d ? d->last_rule7 : LIFE_EINVAL; }
 
 int life_dev_population(life_dev *d, int64_t *counts, int64_t max, int64_t *generations) {
     if (!d || max < 0 || (!counts && max > 0)) return LIFE_EINVAL;

@@ -48,6 +48,8 @@ OPT_DEEP_HALO = 9
 OPT_PIPELINE = 11  # 0 off, 1 automatic, 3..16 row regions per pass (LIFE_OPT_PIPELINE)
 OPT_SKIP_DEAD = 12  # 0 off, 1 run only the tiles whose window may hold a live cell (LIFE_OPT_SKIP_DEAD)
 OPT_POPULATION = 13  # 0 off, 1 record the population of every generation of a step call (LIFE_OPT_POPULATION)
+OPT_RULE7 = 14  # B3/S23 in 7 gates per dword: RULE7_TILES | RULE7_FLOW, 0 the 8-gate kernels (LIFE_OPT_RULE7)
+RULE7_TILES, RULE7_FLOW = 1, 2
 # LIFE_TEMPORAL_DEPTH(_BYTE): generations per halo exchange of the temporal layouts
 TEMPORAL_DEPTH = {"bit": 32, "byte": 32}
 BLOCK_GENS = {"bit": 12, "byte": 32}  # tiles: default generations per launch at most (LIFE_OPT_BLOCK_GENS)
@@ -78,7 +80,7 @@ ABI_SYMBOLS = (
     "life_dev_clear", "life_dev_set_cells", "life_dev_gather_rect", "life_dev_gather_density",
     "life_dev_upload_bits", "life_dev_set_rect",
     "life_rule_parse", "life_rule_format", "life_dev_set_rule", "life_dev_get_rule",
-    "life_dev_activity", "life_dev_population",
+    "life_dev_activity", "life_dev_population", "life_dev_last_rule_arm",
     "life_batch_query", "life_batch_create", "life_batch_destroy", "life_batch_upload", "life_batch_gather",
     "life_batch_fill_random", "life_batch_set_rule", "life_batch_get_rule", "life_batch_configure",
     "life_batch_step", "life_batch_census", "life_batch_settled", "life_batch_generation", "life_batch_sync",
@@ -201,6 +203,8 @@ def _lib():
             L.life_dev_activity.argtypes = [vp] + [P(i64)] * 4
         if hasattr(L, "life_dev_population"):  # absent from builds that predate LIFE_OPT_POPULATION (A/B runs)
             L.life_dev_population.argtypes = [vp, P(i64), i64, P(i64)]
+        if hasattr(L, "life_dev_last_rule_arm"):  # absent from builds that predate LIFE_OPT_RULE7 (A/B runs)
+            L.life_dev_last_rule_arm.argtypes = [vp]
         if hasattr(L, "life_batch_create"):  # absent from builds that predate batches (LIFE_MI355X_LIB A/B runs)
             u32, u64 = ctypes.c_uint32, ctypes.c_uint64
             L.life_batch_query.argtypes = [i64, i64, P(ctypes.c_int), P(i64)]
@@ -587,6 +591,11 @@ class Life:
     def last_path(self) -> str:
         """Kernel family of the last step call (life_dev_last_path)."""
         return PATHS[_check(_lib().life_dev_last_path(self._h), "last_path")]
+
+    def last_rule7(self) -> int:
+        """The forms (RULE7_TILES | RULE7_FLOW) of which a launch of the last step call ran the 7-gate
+        arm of the B3/S23 bit tiles (life_dev_last_rule_arm); 0: every launch ran the 8-gate kernels."""
+        return _check(_lib().life_dev_last_rule_arm(self._h), "last_rule7")
 
     def activity(self):
         """(passes, tiles_run, tiles_cleared, tiles_total) summed over the
