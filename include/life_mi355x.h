@@ -152,6 +152,25 @@ int life_layout_query(int64_t nx, int64_t ny, int dims0, int dims1, int rank, in
 int life_rule_parse(const char *text, uint32_t *birth, uint32_t *survive);
 int life_rule_format(uint32_t birth, uint32_t survive, char out[24]);
 
+/* Generations rules (the batch's wave tier runs them:
+ * life_batch_set_rule_gen).  A cell state is s in [0, states), 2 <= states <=
+ * LIFE_GEN_MAX_STATES: 0 dead, 1 alive, 2 .. states - 1 dying.  With n the
+ * number of the 8 neighbours whose state is exactly 1: s = 0 becomes 1 if
+ * `birth` bit n is set, else stays 0; s = 1 stays 1 if `survive` bit n is set,
+ * else becomes 2 mod states; s >= 2 becomes (s + 1) mod states.  states = 2 is
+ * the Life-like rule of the two masks.  life_rule_parse_gen accepts everything
+ * life_rule_parse accepts (states = 2), "B2/S345/C4" with G accepted for C in
+ * either letter case, and Golly's "345/2/4" (S/B/C); the state count is one or
+ * two decimal digits without a leading zero.  States outside 2 .. 16, an empty
+ * third part, a fourth part or trailing junk are LIFE_EINVAL with a
+ * life_last_error() message that quotes the text.  life_rule_format_gen writes
+ * the canonical "B.../S.../Cn", and for states = 2 exactly what
+ * life_rule_format writes (LIFE_EINVAL for bits above 8 or states outside 2 ..
+ * 16).  Neither needs a GPU. */
+#define LIFE_GEN_MAX_STATES 16
+int life_rule_parse_gen(const char *text, uint32_t *birth, uint32_t *survive, uint32_t *states);
+int life_rule_format_gen(uint32_t birth, uint32_t survive, uint32_t states, char out[32]);
+
 const char *life_strerror(int err);
 const char *life_dev_strerror(int err); /* the same (SURVEY 8(b)'s name for it) */
 const char *life_last_error(void); /* detail of the last LIFE_EHIP/ERCCL on this thread */
@@ -677,6 +696,58 @@ int life_batch_get_rule(life_batch *b, uint32_t *birth, uint32_t *survive);
  * the one rule.  Either out pointer may be NULL.  Blocking. */
 int life_batch_set_rules(life_batch *b, int64_t first, int64_t n, const uint32_t *birth, const uint32_t *survive);
 int life_batch_get_rules(life_batch *b, int64_t first, int64_t n, uint32_t *birth, uint32_t *survive);
+/* Generations rules on the wave tier (semantics: life_rule_
+ * parse_gen above).  life_batch_set_rule_gen is life_batch_set_rule with a
+ * state count: it refuses what that refuses, states outside 2 .. LIFE_GEN_MAX_
+ * STATES, and states > 2 on a group-tier batch (LIFE_EINVAL with a message,
+ * nothing changed); with states = 2 it is life_batch_set_rule.  life_batch_
+ * set_rules_gen is life_batch_set_rules with a state count per universe, under
+ * the same conventions (the first offending entry is named, nothing changed;
+ * the batch is "mixed" afterwards); the table entry stays 8 B, the state count
+ * in the high half of the birth word.  life_batch_set_rules writes states = 2.
+ * The get calls mirror life_batch_get_rule (LIFE_ESTATE on a mixed batch) and
+ * life_batch_get_rules; any out pointer may be NULL.  While the uniform rule
+ * has states > 2, life_batch_get_rule returns LIFE_ESTATE (ask life_batch_
+ * get_rule_gen).
+ * EVERY set-rule call, old or new, resets the dying cells of the universes it
+ * covers to dead (life_batch_set_rule and _set_rule_gen: all of them; the
+ * _set_rules forms: their range) and leaves the alive cells untouched, beside
+ * clearing the settled and cycle flags as documented above: no universe ever
+ * holds a state at or above its state count.
+ * Storage: the alive plane is the batch's storage as before (life_batch_query's
+ * bytes_per_universe stays the alive plane's).  The dying cells live in 1
+ * (states <= 3), 2 (<= 5) or 4 (<= 16) extra bit planes of the same word
+ * layout, plane-major, each bytes_per_universe x count bytes, as many as the
+ * largest state count the batch has seen since it last was two-state needs:
+ * allocated, zeroed, when a rule with states > 2 first arrives, grown when a
+ * larger one does, released when life_batch_set_rule (or _set_rule_gen with
+ * states = 2) returns the batch to two states.  A batch that never saw such a
+ * rule allocates nothing and runs the kernels it ran before.
+ * The older calls keep their meaning, applied to the alive plane: life_batch_
+ * upload (nonzero = alive) clears the dying cells of the universes it writes,
+ * life_batch_gather returns 0 / 1 of "alive", life_batch_census counts the
+ * alive cells and sums over them, life_batch_fill_random gives a random alive
+ * plane with nothing dying.  LIFE_BATCH_OPT_SETTLE and LIFE_BATCH_OPT_CYCLE
+ * compare the whole state, every plane.
+ * life_batch_upload_states / life_batch_gather_states are upload / gather with
+ * the state s itself in every byte.  The upload checks on the host, before
+ * anything is written, that every byte is below the state count of its
+ * universe: LIFE_EINVAL naming the universe and the value otherwise.
+ * life_batch_census_gen: per universe, `count` entries each, any may be NULL:
+ * the cells with s = 1, the cells with s >= 2, and the sum over all cells of s
+ * x mix64(y * nx + x + 1) mod 2^64 (life_batch_census's checksum where nothing
+ * is dying).  Blocking.
+ * Out of scope: Generations on the group tier, on life_dev and in the driver;
+ * B0; more than 16 states; random fills of dying cells. */
+int life_batch_set_rule_gen(life_batch *b, uint32_t birth, uint32_t survive, uint32_t states);
+int life_batch_get_rule_gen(life_batch *b, uint32_t *birth, uint32_t *survive, uint32_t *states);
+int life_batch_set_rules_gen(life_batch *b, int64_t first, int64_t n, const uint32_t *birth, const uint32_t *survive,
+                             const uint32_t *states);
+int life_batch_get_rules_gen(life_batch *b, int64_t first, int64_t n, uint32_t *birth, uint32_t *survive,
+                             uint32_t *states);
+int life_batch_upload_states(life_batch *b, int64_t first, int64_t n, const uint8_t *grids);
+int life_batch_gather_states(life_batch *b, int64_t first, int64_t n, uint8_t *grids);
+int life_batch_census_gen(life_batch *b, int64_t *live, int64_t *dying, uint64_t *checksum);
 /* LIFE_BATCH_OPT_SETTLE (wave tier, value 0 / 1, default 0): while on, a wave
  * compares its universe after each generation of a step call, from the call's
  * second on, with the state two generations earlier.  At the first generation

@@ -33,6 +33,16 @@ struct life_batch {
     bool cycle = false;
     int64_t *cycles = nullptr;  // period[count], found[count] of LIFE_BATCH_OPT_CYCLE (from its first use)
     int64_t generation = 0;
+    // Generations.  `states` is the uniform rule's; on a mixed batch `shadow` holds every
+    // universe's and `hist` how many universes have each count.  `decay`: `planes` (0, 1, 2, 4) bit planes of d = s
+    // - 1 of the dying cells, each as large as `cells`, plane-major; as many as the largest state count since the
+    // batch last was two-state needs.
+    uint32_t states = 2;
+    std::vector<uint8_t> shadow;
+    int64_t hist[life::kGenMaxStates + 1] = {};
+    uint32_t *decay = nullptr;
+    int planes = 0;
+    unsigned long long *census_gen = nullptr;  // live[count], dying[count], checksum[count] of life_batch_census_gen
 };
 
 namespace {
@@ -69,10 +79,59 @@ int clear_settled(life_batch *b, int64_t first, int64_t n) {
     return LIFE_OK;
 }
 
-// bits above 8 and B0, as life_batch_set_rule refuses them; `at` >= 0: an entry of life_batch_set_rules
-int rule_ok(uint32_t birth, uint32_t survive, int64_t at) {
-    char where[48] = "";
-    if (at >= 0) snprintf(where, sizeof where, "life_batch_set_rules: entry %lld: ", (long long)at);
+// the largest state count of the batch's universes, and the state count of one
+uint32_t max_states(const life_batch *b) {
+    if (b->shadow.empty()) return b->states;
+    uint32_t c = life::kGenMaxStates;
+    while (c > 2 && b->hist[c] == 0) --c;
+    return c;
+}
+uint32_t states_of(const life_batch *b, int64_t u) { return b->shadow.empty() ? b->states : b->shadow[(size_t)u]; }
+
+// the dying cells of universes [first, first + n) to dead, in every plane
+int clear_decay(life_batch *b, int64_t first, int64_t n) {
+    if (!b->decay || n < 1) return LIFE_OK;
+    const size_t plane = words_of(b, b->count);
+    for (int p = 0; p < b->planes; p++)
+        HIPCHK(hipMemsetAsync(b->decay + (size_t)p * plane + words_of(b, first), 0, 4 * words_of(b, n), b->stream));
+    return LIFE_OK;
+}
+
+// at least `need` decay planes: the new ones zero, the old ones kept (plane-major: they are a prefix)
+int grow_decay(life_batch *b, int need) {
+    if (b->planes >= need) return LIFE_OK;
+    const size_t plane = 4 * words_of(b, b->count);
+    uint32_t *grown = nullptr;
+    HIPCHK(hipMalloc(&grown, plane * (size_t)need));
+    hipError_t e = hipMemsetAsync(grown, 0, plane * (size_t)need, b->stream);
+    if (e == hipSuccess && b->planes)
+        e = hipMemcpyAsync(grown, b->decay, plane * (size_t)b->planes, hipMemcpyDeviceToDevice, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(grown);
+        HIPCHK(e);
+    }
+    if (b->decay) HIPCHK(hipFree(b->decay));
+    b->decay = grown;
+    b->planes = need;
+    return LIFE_OK;
+}
+
+// the batch is two-state again: the planes are released
+int drop_decay(life_batch *b) {
+    if (!b->decay) return LIFE_OK;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(hipFree(b->decay));
+    b->decay = nullptr;
+    b->planes = 0;
+    return LIFE_OK;
+}
+
+// bits above 8 and B0, as life_batch_set_rule refuses them; `at` >= 0: an entry of `call` (life_batch_set_rules
+// or its _gen form)
+int rule_ok(uint32_t birth, uint32_t survive, int64_t at, const char *call = "life_batch_set_rules") {
+    char where[56] = "";
+    if (at >= 0) snprintf(where, sizeof where, "%s: entry %lld: ", call, (long long)at);
     if ((birth | survive) & ~life::kRuleMask) {
         set_err("%srule masks 0x%x / 0x%x: bits above 8", where, birth, survive);
         return LIFE_EINVAL;
@@ -88,6 +147,8 @@ int rule_ok(uint32_t birth, uint32_t survive, int64_t at) {
 
 // the table of a mixed batch is released: the batch is uniform again
 int drop_rules(life_batch *b) {
+    b->shadow.clear();
+    b->shadow.shrink_to_fit();
     if (!b->rules) return LIFE_OK;
     HIPCHK(hipStreamSynchronize(b->stream));
     HIPCHK(hipFree(b->rules));
@@ -101,7 +162,9 @@ void free_batch(life_batch *b) {
     if (b->settled) (void)hipFree(b->settled);
     if (b->rules) (void)hipFree(b->rules);
     if (b->cycles) (void)hipFree(b->cycles);
+    if (b->decay) (void)hipFree(b->decay);
     if (b->census) (void)hipFree(b->census);
+    if (b->census_gen) (void)hipFree(b->census_gen);
     if (b->stage) (void)hipFree(b->stage);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
@@ -127,6 +190,116 @@ int create(life_batch *b) {
     HIPCHK(hipMemsetAsync(b->cells, 0, bytes, b->stream));
     CHK(clear_settled(b, 0, b->count));
     HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+// states outside 2 .. 16, and more than two on a group-tier batch; `at` as rule_ok's
+int states_ok(const life_batch *b, uint32_t birth, uint32_t survive, uint32_t states, int64_t at, const char *call) {
+    char where[56] = "";
+    if (at >= 0) snprintf(where, sizeof where, "%s: entry %lld: ", call, (long long)at);
+    if (states < 2 || states > life::kGenMaxStates) {
+        char name[24];
+        life::rule_format(birth, survive, name);
+        set_err("%srule %s with %u states (2 .. %u)", where, name, states, life::kGenMaxStates);
+        return LIFE_EINVAL;
+    }
+    if (states > 2 && b->plan.tier != LIFE_BATCH_TIER_WAVE) {
+        char name[32];
+        life::rule_format_gen(birth, survive, states, name);
+        set_err("%srule %s: a group-tier batch (%lld x %lld) has two states (Generations rules are a feature of the "
+                "wave tier)", where, name, (long long)b->nx, (long long)b->ny);
+        return LIFE_EINVAL;
+    }
+    return LIFE_OK;
+}
+
+// life_batch_set_rules (states null: two each) and life_batch_set_rules_gen
+int set_rules(life_batch *b, int64_t first, int64_t n, const uint32_t *birth, const uint32_t *survive,
+              const uint32_t *states, const char *call) {
+    if (!b) return LIFE_EINVAL;
+    CHK(range_ok(b, first, n, birth && survive ? (const void *)birth : nullptr, call));
+    if (n == 0) return LIFE_OK;
+    const bool wave = b->plan.tier == LIFE_BATCH_TIER_WAVE;
+    uint32_t most = 2;
+    for (int64_t k = 0; k < n; k++) {
+        CHK(rule_ok(birth[k], survive[k], k, call));
+        if (states) CHK(states_ok(b, birth[k], survive[k], states[k], k, call));
+        if (states && states[k] > most) most = states[k];
+        if (!wave && (birth[k] != life::kConwayBirth || survive[k] != life::kConwaySurvive)) {
+            char name[24];
+            life::rule_format(birth[k], survive[k], name);
+            set_err("%s: entry %lld: rule %s: a group-tier batch (%lld x %lld) runs B3/S23 only "
+                    "(rules are a feature of the wave tier)", call, (long long)k, name, (long long)b->nx,
+                    (long long)b->ny);
+            return LIFE_EINVAL;
+        }
+    }
+    HIPCHK(hipSetDevice(b->device));
+    if (wave) {
+        CHK(grow_decay(b, life::gen_planes(most)));
+        // the first call lays the whole table down: the uniform rule, then the range
+        const bool fresh = !b->rules;
+        const int64_t lo = fresh ? 0 : first, m = fresh ? b->count : n;
+        std::vector<uint32_t> host((size_t)(2 * m));
+        uint32_t *table = b->rules;
+        if (fresh) {
+            HIPCHK(hipMalloc(&table, 2 * sizeof(uint32_t) * (size_t)b->count));
+            for (int64_t u = 0; u < m; u++) {
+                host[2 * u] = b->birth | b->states << 16;
+                host[2 * u + 1] = b->survive;
+            }
+        }
+        for (int64_t k = 0; k < n; k++) {
+            host[2 * (first - lo + k)] = birth[k] | (states ? states[k] : 2u) << 16;
+            host[2 * (first - lo + k) + 1] = survive[k];
+        }
+        // waited for: `host` leaves scope, and a table that did not arrive is not kept
+        hipError_t e = hipMemcpyAsync(table + 2 * lo, host.data(), sizeof(uint32_t) * host.size(),
+                                      hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+        if (e != hipSuccess && fresh) (void)hipFree(table);
+        HIPCHK(e);
+        b->rules = table;
+        if (fresh) {
+            b->shadow.assign((size_t)b->count, (uint8_t)b->states);
+            for (int64_t &h : b->hist) h = 0;
+            b->hist[b->states] = b->count;
+        }
+        for (int64_t k = 0; k < n; k++) {
+            uint8_t &c = b->shadow[(size_t)(first + k)];
+            b->hist[c]--;
+            c = (uint8_t)(states ? states[k] : 2u);
+            b->hist[c]++;
+        }
+        CHK(clear_decay(b, first, n));
+        return clear_settled(b, first, n);
+    }
+    return clear_settled(b, first, n);
+}
+
+int get_rules(life_batch *b, int64_t first, int64_t n, uint32_t *birth, uint32_t *survive, uint32_t *states,
+              const char *call) {
+    if (!b) return LIFE_EINVAL;
+    CHK(range_ok(b, first, n, b, call));
+    if (n == 0) return LIFE_OK;
+    if (!b->rules) {
+        for (int64_t k = 0; k < n; k++) {
+            if (birth) birth[k] = b->birth;
+            if (survive) survive[k] = b->survive;
+            if (states) states[k] = b->states;
+        }
+        return LIFE_OK;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    std::vector<uint32_t> host((size_t)(2 * n));
+    HIPCHK(hipMemcpyAsync(host.data(), b->rules + 2 * first, sizeof(uint32_t) * host.size(), hipMemcpyDeviceToHost,
+                          b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int64_t k = 0; k < n; k++) {
+        if (birth) birth[k] = host[2 * k] & 0xFFFFu;  // (the state count rides in the high half)
+        if (survive) survive[k] = host[2 * k + 1];
+        if (states) states[k] = host[2 * k] >> 16;
+    }
     return LIFE_OK;
 }
 
@@ -179,6 +352,7 @@ int life_batch_upload(life_batch *b, int64_t first, int64_t n, const uint8_t *gr
     // this call returns, so the caller may reuse it at once
     HIPCHK(hipMemcpyAsync(b->stage, grids, bytes, hipMemcpyHostToDevice, b->stream));
     HIPCHK(life::launch_batch_import(b->plan, b->nx, b->ny, n, b->stage, b->cells + words_of(b, first), b->stream));
+    CHK(clear_decay(b, first, n));
     CHK(clear_settled(b, first, n));
     b->census_valid = false;
     if (n == b->count) b->generation = 0;
@@ -203,6 +377,7 @@ int life_batch_fill_random(life_batch *b, uint64_t seed, uint32_t thr32) {
     if (!b) return LIFE_EINVAL;
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(life::launch_batch_fill(b->plan, b->nx, b->ny, b->count, seed, thr32, b->cells, b->stream));
+    CHK(clear_decay(b, 0, b->count));
     CHK(clear_settled(b, 0, b->count));
     b->census_valid = false;
     b->generation = 0;
@@ -222,9 +397,11 @@ int life_batch_set_rule(life_batch *b, uint32_t birth, uint32_t survive) {
     }
     HIPCHK(hipSetDevice(b->device));
     CHK(drop_rules(b));
+    CHK(drop_decay(b));
     CHK(clear_settled(b, 0, b->count));
     b->birth = birth;
     b->survive = survive;
+    b->states = 2;
     b->table = !conway;
     if (b->table) b->words = life::rule_words(birth, survive);
     return LIFE_OK;
@@ -237,76 +414,128 @@ int life_batch_get_rule(life_batch *b, uint32_t *birth, uint32_t *survive) {
                 "life_batch_get_rules");
         return LIFE_ESTATE;
     }
+    if (b->states > 2) {
+        set_err("life_batch_get_rule: the batch runs a Generations rule of %u states (life_batch_set_rule_gen): ask "
+                "life_batch_get_rule_gen", b->states);
+        return LIFE_ESTATE;
+    }
     if (birth) *birth = b->birth;
     if (survive) *survive = b->survive;
     return LIFE_OK;
 }
 
 int life_batch_set_rules(life_batch *b, int64_t first, int64_t n, const uint32_t *birth, const uint32_t *survive) {
-    if (!b) return LIFE_EINVAL;
-    CHK(range_ok(b, first, n, birth && survive ? (const void *)birth : nullptr, "life_batch_set_rules"));
-    if (n == 0) return LIFE_OK;
-    const bool wave = b->plan.tier == LIFE_BATCH_TIER_WAVE;
-    for (int64_t k = 0; k < n; k++) {
-        CHK(rule_ok(birth[k], survive[k], k));
-        if (!wave && (birth[k] != life::kConwayBirth || survive[k] != life::kConwaySurvive)) {
-            char name[24];
-            life::rule_format(birth[k], survive[k], name);
-            set_err("life_batch_set_rules: entry %lld: rule %s: a group-tier batch (%lld x %lld) runs B3/S23 only "
-                    "(rules are a feature of the wave tier)", (long long)k, name, (long long)b->nx, (long long)b->ny);
-            return LIFE_EINVAL;
-        }
-    }
-    HIPCHK(hipSetDevice(b->device));
-    if (wave) {
-        // the first call lays the whole table down: the uniform rule, then the range
-        const bool fresh = !b->rules;
-        const int64_t lo = fresh ? 0 : first, m = fresh ? b->count : n;
-        std::vector<uint32_t> host((size_t)(2 * m));
-        uint32_t *table = b->rules;
-        if (fresh) {
-            HIPCHK(hipMalloc(&table, 2 * sizeof(uint32_t) * (size_t)b->count));
-            for (int64_t u = 0; u < m; u++) {
-                host[2 * u] = b->birth;
-                host[2 * u + 1] = b->survive;
-            }
-        }
-        for (int64_t k = 0; k < n; k++) {
-            host[2 * (first - lo + k)] = birth[k];
-            host[2 * (first - lo + k) + 1] = survive[k];
-        }
-        // waited for: `host` leaves scope, and a table that did not arrive is not kept
-        hipError_t e = hipMemcpyAsync(table + 2 * lo, host.data(), sizeof(uint32_t) * host.size(),
-                                      hipMemcpyHostToDevice, b->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-        if (e != hipSuccess && fresh) (void)hipFree(table);
-        HIPCHK(e);
-        b->rules = table;
-        return clear_settled(b, first, n);
-    }
-    return clear_settled(b, first, n);
+    return set_rules(b, first, n, birth, survive, nullptr, "life_batch_set_rules");
 }
 
 int life_batch_get_rules(life_batch *b, int64_t first, int64_t n, uint32_t *birth, uint32_t *survive) {
+    return get_rules(b, first, n, birth, survive, nullptr, "life_batch_get_rules");
+}
+
+int life_batch_set_rule_gen(life_batch *b, uint32_t birth, uint32_t survive, uint32_t states) {
     if (!b) return LIFE_EINVAL;
-    CHK(range_ok(b, first, n, b, "life_batch_get_rules"));
-    if (n == 0) return LIFE_OK;
-    if (!b->rules) {
-        for (int64_t k = 0; k < n; k++) {
-            if (birth) birth[k] = b->birth;
-            if (survive) survive[k] = b->survive;
-        }
-        return LIFE_OK;
-    }
+    CHK(rule_ok(birth, survive, -1));
+    CHK(states_ok(b, birth, survive, states, -1, "life_batch_set_rule_gen"));
+    if (states == 2) return life_batch_set_rule(b, birth, survive);
     HIPCHK(hipSetDevice(b->device));
-    std::vector<uint32_t> host((size_t)(2 * n));
-    HIPCHK(hipMemcpyAsync(host.data(), b->rules + 2 * first, sizeof(uint32_t) * host.size(), hipMemcpyDeviceToHost,
-                          b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (int64_t k = 0; k < n; k++) {
-        if (birth) birth[k] = host[2 * k];
-        if (survive) survive[k] = host[2 * k + 1];
+    CHK(grow_decay(b, life::gen_planes(states)));
+    CHK(drop_rules(b));
+    CHK(clear_decay(b, 0, b->count));
+    CHK(clear_settled(b, 0, b->count));
+    b->birth = birth;
+    b->survive = survive;
+    b->states = states;
+    b->table = true;  // (what a return to two states by life_batch_set_rule recomputes)
+    b->words = life::rule_words(birth, survive);
+    return LIFE_OK;
+}
+
+int life_batch_get_rule_gen(life_batch *b, uint32_t *birth, uint32_t *survive, uint32_t *states) {
+    if (!b) return LIFE_EINVAL;
+    if (b->rules) {
+        set_err("life_batch_get_rule_gen: the batch holds a rule per universe (life_batch_set_rules): ask "
+                "life_batch_get_rules_gen");
+        return LIFE_ESTATE;
     }
+    if (birth) *birth = b->birth;
+    if (survive) *survive = b->survive;
+    if (states) *states = b->states;
+    return LIFE_OK;
+}
+
+int life_batch_set_rules_gen(life_batch *b, int64_t first, int64_t n, const uint32_t *birth, const uint32_t *survive,
+                             const uint32_t *states) {
+    if (!b) return LIFE_EINVAL;
+    if (n > 0 && !states) {
+        set_err("life_batch_set_rules_gen: no states");
+        return LIFE_EINVAL;
+    }
+    return set_rules(b, first, n, birth, survive, states, "life_batch_set_rules_gen");
+}
+
+int life_batch_get_rules_gen(life_batch *b, int64_t first, int64_t n, uint32_t *birth, uint32_t *survive,
+                             uint32_t *states) {
+    return get_rules(b, first, n, birth, survive, states, "life_batch_get_rules_gen");
+}
+
+int life_batch_upload_states(life_batch *b, int64_t first, int64_t n, const uint8_t *grids) {
+    if (!b) return LIFE_EINVAL;
+    CHK(range_ok(b, first, n, grids, "life_batch_upload_states"));
+    if (n == 0) return LIFE_OK;
+    const size_t cells = (size_t)(b->nx * b->ny);
+    for (int64_t k = 0; k < n; k++) {
+        const uint32_t c = states_of(b, first + k);
+        const uint8_t *g = grids + (size_t)k * cells;
+        for (size_t i = 0; i < cells; i++)
+            if (g[i] >= c) {
+                set_err("life_batch_upload_states: universe %lld: cell (%lld, %lld) holds %u, its rule has %u states",
+                        (long long)(first + k), (long long)(i % (size_t)b->nx), (long long)(i / (size_t)b->nx), g[i],
+                        c);
+                return LIFE_EINVAL;
+            }
+    }
+    if (!b->decay) return life_batch_upload(b, first, n, grids);  // every byte is 0 or 1
+    HIPCHK(hipSetDevice(b->device));
+    const size_t bytes = (size_t)n * cells;
+    CHK(stage_for(b, bytes));
+    HIPCHK(hipMemcpyAsync(b->stage, grids, bytes, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(life::launch_batch_import_states(b->plan, b->nx, b->ny, b->count, first, n, b->stage, b->cells, b->decay,
+                                            b->planes, b->stream));
+    CHK(clear_settled(b, first, n));
+    b->census_valid = false;
+    if (n == b->count) b->generation = 0;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+int life_batch_gather_states(life_batch *b, int64_t first, int64_t n, uint8_t *grids) {
+    if (!b) return LIFE_EINVAL;
+    CHK(range_ok(b, first, n, grids, "life_batch_gather_states"));
+    if (n == 0) return LIFE_OK;
+    if (!b->decay) return life_batch_gather(b, first, n, grids);
+    HIPCHK(hipSetDevice(b->device));
+    const size_t bytes = (size_t)n * (size_t)(b->nx * b->ny);
+    CHK(stage_for(b, bytes));
+    HIPCHK(life::launch_batch_export_states(b->plan, b->nx, b->ny, b->count, first, n, b->cells, b->decay, b->planes,
+                                            b->stage, b->stream));
+    HIPCHK(hipMemcpyAsync(grids, b->stage, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+int life_batch_census_gen(life_batch *b, int64_t *live, int64_t *dying, uint64_t *checksum) {
+    if (!b) return LIFE_EINVAL;
+    HIPCHK(hipSetDevice(b->device));
+    const size_t bytes = sizeof(unsigned long long) * (size_t)b->count;
+    if (!b->census_gen) HIPCHK(hipMalloc(&b->census_gen, 3 * bytes));
+    unsigned long long *d_live = b->census_gen, *d_dying = d_live + b->count, *d_sum = d_dying + b->count;
+    // (not cached: a call costs one pass over the planes)
+    HIPCHK(life::launch_batch_census_states(b->plan, b->nx, b->ny, b->count, b->cells, b->decay, b->planes, d_live,
+                                            d_dying, d_sum, b->stream));
+    if (live) HIPCHK(hipMemcpyAsync(live, d_live, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (dying) HIPCHK(hipMemcpyAsync(dying, d_dying, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (checksum) HIPCHK(hipMemcpyAsync(checksum, d_sum, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
     return LIFE_OK;
 }
 
@@ -353,7 +582,13 @@ int life_batch_step(life_batch *b, int64_t generations) {
     }
     if (generations == 0) return LIFE_OK;
     HIPCHK(hipSetDevice(b->device));
-    if (b->plan.tier == LIFE_BATCH_TIER_WAVE && (b->rules || b->cycle))
+    const uint32_t most = max_states(b);
+    if (most > 2)  // (wave tier: no other takes such a rule)
+        HIPCHK(life::launch_batch_gen(b->plan, b->nx, b->ny, b->count, b->cells, b->decay, life::gen_planes(most),
+                                      generations, b->birth, b->survive, b->states, b->rules, b->settle, b->settled,
+                                      b->cycle, b->cycles, b->cycles ? b->cycles + b->count : nullptr, b->generation,
+                                      b->stream));
+    else if (b->plan.tier == LIFE_BATCH_TIER_WAVE && (b->rules || b->cycle))
         HIPCHK(life::launch_batch_survey(b->plan, b->nx, b->ny, b->count, b->cells, generations,
                                          b->table ? &b->words : nullptr, b->rules, b->settle, b->settled, b->cycle,
                                          b->cycles, b->cycles ? b->cycles + b->count : nullptr, b->generation,

@@ -28,6 +28,17 @@ hipError_t launch_batch_wave(const BatchPlan &p, int64_t nx, int64_t ny, int64_t
 hipError_t launch_batch_survey(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
                                const RuleWords *rule, const uint32_t *rules, bool settle, int64_t *settled, bool cycle,
                                int64_t *period, int64_t *found, int64_t gen0, hipStream_t s);
+// Generations on the wave tier, a kernel family of its own:
+// `decay` holds `planes` (1, 2 or 4) bit planes of d = s - 1 of the dying
+// cells, each count * ny * p.words words, plane-major, beside the alive plane
+// `cells`.  rules null: the uniform (birth, survive, states); else the table
+// of life_batch_set_rules_gen, universe u's (birth | states << 16, survive) at
+// rules[2 u], and every state count must fit `planes` (life::gen_planes).  The
+// detectors are launch_batch_survey's, comparing every plane.
+hipError_t launch_batch_gen(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, uint32_t *decay,
+                            int planes, int64_t gens, uint32_t birth, uint32_t survive, uint32_t states,
+                            const uint32_t *rules, bool settle, int64_t *settled, bool cycle, int64_t *period,
+                            int64_t *found, int64_t gen0, hipStream_t s);
 // Group tier (B3/S23): one workgroup per universe.
 hipError_t launch_batch_group(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
                               int64_t gens, hipStream_t s);
@@ -40,6 +51,19 @@ hipError_t launch_batch_import(const BatchPlan &p, int64_t nx, int64_t ny, int64
                                uint32_t *cells, hipStream_t s);
 hipError_t launch_batch_export(const BatchPlan &p, int64_t nx, int64_t ny, int64_t n, const uint32_t *cells,
                                uint8_t *dense, hipStream_t s);
+// The same with the state s of every cell in its byte, universes [first, first
+// + n) of `count`: `cells` and `decay` are the bases of the alive plane and of
+// the `planes` decay planes (0 .. 4; none: decay may be null).  The census
+// counts s = 1 (live), s >= 2 (dying) and sums s * mix64.
+hipError_t launch_batch_import_states(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, int64_t first,
+                                      int64_t n, const uint8_t *dense, uint32_t *cells, uint32_t *decay, int planes,
+                                      hipStream_t s);
+hipError_t launch_batch_export_states(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, int64_t first,
+                                      int64_t n, const uint32_t *cells, const uint32_t *decay, int planes,
+                                      uint8_t *dense, hipStream_t s);
+hipError_t launch_batch_census_states(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, const uint32_t *cells,
+                                      const uint32_t *decay, int planes, unsigned long long *live,
+                                      unsigned long long *dying, unsigned long long *sum, hipStream_t s);
 // universe u = life_dev_fill_random(seed + u, thr32) of an nx x ny grid
 hipError_t launch_batch_fill(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint64_t seed, uint32_t thr32,
                              uint32_t *cells, hipStream_t s);

@@ -419,6 +419,287 @@ __global__ __launch_bounds__(64 * kBatchWaves) void batch_census_kernel(const ui
     }
 }
 
+// ---------------------------------------------------- Generations (wave tier)
+// DESIGN.md 5.13.  A cell state s in [0, C): the alive plane A (s == 1) is the
+// batch storage, d = s - 1 of a dying cell (else 0) is held in P more bit
+// planes of the same word layout, plane p of universe u `plane` words after
+// plane p - 1.  Only A is summed: the funnel shifts and the four ds_bpermute
+// per word are wave_body's, and so is the rule -- n = TableRule(sums, A) is the
+// Life-like successor of a cell that is dead or alive.  Per word then, with
+// `dying` the OR of the d planes:
+//   A'  = n & ~dying                      (a dying cell is not reborn)
+//   d'  = dying ? (d == C - 2 ? 0 : d + 1) : (A & ~n & (C > 2)) ? 1 : 0
+// C - 2 and C > 2 are wave-uniform words expanded before the generation loop
+// beside the rule's leaves, so a C = 2 universe of a mixed batch never starts
+// to decay, and one kernel serves a uniform rule (from the launch arguments)
+// and a rule per universe (from the table).  Lanes at and beyond ny and the
+// padding bits hold zeros in every plane: A is zero there, so nothing starts.
+constexpr uint32_t kGenStart = (0xF0 & ~0xCC & 0xAA) & 0xFF;      // a & ~b & c: alive, not surviving, the rule decays
+constexpr uint32_t kGenAndNot = (0xF0 & ~(0xCC | 0xAA)) & 0xFF;   // a & ~(b | c)
+constexpr uint32_t kGenOrXor = (0xF0 | (0xCC ^ 0xAA)) & 0xFF;     // a | (b ^ c)
+constexpr uint32_t kGenOrAnd = ((0xF0 | 0xCC) & 0xAA) & 0xFF;     // (a | b) & c
+constexpr uint32_t kGenXorAnd = ((0xF0 ^ 0xCC) & 0xAA) & 0xFF;    // (a ^ b) & c
+constexpr uint32_t kGenAndNotOr = ((0xF0 & ~0xCC) | 0xAA) & 0xFF; // (a & ~b) | c
+constexpr uint32_t kGenOr3 = (0xF0 | 0xCC | 0xAA) & 0xFF;
+constexpr uint32_t kGenAnd3 = (0xF0 & 0xCC & 0xAA) & 0xFF;
+
+struct BNArgs {
+    uint32_t *cells, *decay;
+    int64_t plane;  // words between two decay planes
+    int64_t *settled;
+    int64_t count, gen0;
+    int32_t nx, ny, gens;
+    uint32_t birth, survive;  // the uniform rule, as a table entry (rules null)
+    const uint2 *rules;       // (birth | states << 16, survive) of universe u
+    int64_t *period, *found;
+};
+
+template <int W, int P, int DET>
+__global__ __launch_bounds__(64 * kBatchWaves) void batch_gen_kernel(BNArgs a) {
+    constexpr bool SETTLE = DET == kSettle, CYCLE = DET == kCycle;
+    constexpr int N = W * (1 + P);  // state words of a lane: v[j] alive, v[W (1 + p) + j] plane p of d
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t u = (int64_t)blockIdx.x * kBatchWaves + (int64_t)(threadIdx.x >> 6);
+    if (u >= a.count) return;  // the whole wave
+    uint2 m = make_uint2(a.birth, a.survive);
+    if (a.rules) m = a.rules[u];
+    const TableRule rp = universe_rule(&m, 0);  // (the leaves read bits 0 .. 8 of a mask: the state count rides above)
+    // d of the last dying state, bit p spread over a word, and "this universe decays at all"
+    const uint32_t states = m.x >> 16;
+    const uint32_t top = states > 2u ? states - 2u : 0u;
+    const uint32_t decays = states > 2u ? 0xFFFFFFFFu : 0u;
+    uint32_t L[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) L[p] = (top >> p) & 1u ? 0xFFFFFFFFu : 0u;
+
+    const int ny = a.ny;
+    const bool active = lane < ny;
+    const int up = !active ? lane : lane == 0 ? ny - 1 : lane - 1;
+    const int dn = !active ? lane : lane + 1 == ny ? 0 : lane + 1;
+    const int addr_up = up << 2, addr_dn = dn << 2;
+    const XWrap xw(a.nx, W);
+    const size_t at = ((size_t)u * (size_t)ny + (size_t)lane) * W;
+
+    uint32_t v[N];
+#pragma unroll
+    for (int j = 0; j < W; ++j) v[j] = active ? a.cells[at + j] : 0u;
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[W * (1 + p) + j] = active ? a.decay[(size_t)p * (size_t)a.plane + at + j] : 0u;
+
+    int gens = a.gens;
+    bool detect = false;
+    if (SETTLE) {
+        detect = a.settled[u] < 0;
+        if (!detect) gens &= 1;  // settled in an earlier call: the state has period 1 or 2
+    }
+    uint32_t p1[SETTLE ? N : 1], p2[SETTLE ? N : 1];  // S_(g-1), S_(g-2), every plane
+    if (SETTLE) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) p1[i] = p2[i] = v[i];
+    }
+    uint32_t T[CYCLE ? N : 1];  // Brent's checkpoint, every plane (wave_body)
+    uint32_t power = 1, lam = 0;
+    if (CYCLE) {
+        const uint32_t known = __builtin_amdgcn_readfirstlane((uint32_t)a.period[u]);
+        detect = known == 0u;
+        if (!detect) gens = (int)((uint32_t)gens % known);  // found in an earlier call
+#pragma unroll
+        for (int i = 0; i < N; ++i) T[i] = v[i];
+    }
+    auto generation = [&]() {
+        uint32_t s0[W], s1[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const uint32_t l = j == 0 ? v[W - 1] << xw.lsh : v[j - 1];
+            const uint32_t r = j == W - 1 ? v[0] : v[j + 1];
+            uint32_t c = v[j];
+            if (j == W - 1) c = b3<kKeepMux>(c, xw.keep, v[0] << xw.qs);
+            BitEnc::fa(__builtin_amdgcn_alignbit(c, l, 31), c, __builtin_amdgcn_alignbit(r, c, 1), s0[j], s1[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const uint32_t a0 = bperm(addr_up, s0[j]), a1 = bperm(addr_up, s1[j]);
+            const uint32_t d0 = bperm(addr_dn, s0[j]), d1 = bperm(addr_dn, s1[j]);
+            const uint32_t alive = v[j];
+            const uint32_t n = rp(a0, a1, s0[j], s1[j], d0, d1, alive);
+            uint32_t *d = &v[W + j];  // plane p at d[W p]
+            const uint32_t start = b3<kGenStart>(alive, n, decays);
+            if (P == 1) {  // d is 0 or 1 = C - 2: a dying cell dies, 2 v_bitop3
+                v[j] = b3<kGenAndNot>(n, d[0], d[0]);
+                d[0] = start;
+            } else if (P == 2) {  // 6 and a v_xor
+                v[j] = b3<kGenAndNot>(n, d[0], d[W]);
+                const uint32_t more = b3<kGenOrXor>(d[0] ^ L[0], d[W], L[1]);     // d != C - 2
+                const uint32_t go = b3<kGenOrAnd>(d[0], d[W], more);              // dying, and not for the last time
+                const uint32_t t1 = b3<kGenXorAnd>(d[W], d[0], go);
+                d[0] = b3<kGenAndNotOr>(go, d[0], start);
+                d[W] = t1;
+            } else {  // 12, a v_xor and a v_and
+                const uint32_t low = b3<kGenOr3>(d[0], d[W], d[2 * W]);
+                v[j] = b3<kGenAndNot>(n, low, d[3 * W]);
+                uint32_t more = b3<kGenOrXor>(d[0] ^ L[0], d[W], L[1]);
+                more = b3<kGenOrXor>(more, d[2 * W], L[2]);
+                more = b3<kGenOrXor>(more, d[3 * W], L[3]);
+                const uint32_t go = b3<kGenOrAnd>(low, d[3 * W], more);
+                const uint32_t c2 = d[0] & d[W], c3 = b3<kGenAnd3>(d[0], d[W], d[2 * W]);  // the ripple of d + 1
+                const uint32_t t1 = b3<kGenXorAnd>(d[W], d[0], go);
+                d[0] = b3<kGenAndNotOr>(go, d[0], start);
+                d[W] = t1;
+                d[2 * W] = b3<kGenXorAnd>(d[2 * W], c2, go);
+                d[3 * W] = b3<kGenXorAnd>(d[3 * W], c3, go);
+            }
+        }
+        v[W - 1] &= xw.keep;  // (the d planes need none: nothing starts where A is zero)
+    };
+    auto differs = [&](const uint32_t *than) {
+        uint32_t diff = 0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) diff |= v[i] ^ than[i];
+        return __builtin_amdgcn_ballot_w64(diff != 0u) != 0ull;
+    };
+    if (CYCLE) {
+        // as wave_body: the detecting generations, then the rest; what is recorded is written between the loops
+        int rest = gens, g = 1;
+        if (detect) {
+            for (; g <= gens; ++g) {
+                generation();
+                ++lam;
+                if (!differs(T)) break;  // S_g == T in every plane: the minimal period is lam
+                if (lam == power) {
+#pragma unroll
+                    for (int i = 0; i < N; ++i) T[i] = v[i];
+                    power <<= 1;
+                    lam = 0;
+                }
+            }
+            rest = 0;
+            if (g <= gens) {
+                if (lane == 0) {
+                    a.period[u] = (int64_t)lam;
+                    a.found[u] = a.gen0 + g;
+                }
+                rest = (int)((uint32_t)(gens - g) % lam);
+            }
+        }
+        for (g = 0; g < rest; ++g) generation();
+    }
+    for (int g = 1; !CYCLE && g <= gens; ++g) {
+        generation();
+        if (SETTLE && detect) {
+            if (g >= 2 && !differs(p2)) {  // S_g == S_(g-2), the whole wave agrees
+                if (lane == 0) a.settled[u] = a.gen0 + g;
+                detect = false;
+                gens = g + ((gens - g) & 1);
+            }
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                p2[i] = p1[i];
+                p1[i] = v[i];
+            }
+        }
+    }
+    if (!active) return;
+#pragma unroll
+    for (int j = 0; j < W; ++j) a.cells[at + j] = v[j];
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int j = 0; j < W; ++j) a.decay[(size_t)p * (size_t)a.plane + at + j] = v[W * (1 + p) + j];
+}
+
+template <int W, int P>
+hipError_t launch_gen(const BNArgs &a, int det, unsigned blocks, hipStream_t s) {
+    if (det == kCycle)
+        batch_gen_kernel<W, P, kCycle><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
+    else if (det == kSettle)
+        batch_gen_kernel<W, P, kSettle><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
+    else
+        batch_gen_kernel<W, P, kNoDetector><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+// The data movement of the states: one thread per word position of the alive
+// plane, which walks the `planes` decay planes at the same offset.
+// d of the cell at bit k of four plane words
+__device__ __forceinline__ uint32_t plane_bits(const uint32_t (&d)[4], int k) {
+    return ((d[0] >> k) & 1u) | ((d[1] >> k) & 1u) << 1 | ((d[2] >> k) & 1u) << 2 | ((d[3] >> k) & 1u) << 3;
+}
+
+__global__ void batch_import_states_kernel(const uint8_t *dense, uint32_t *cells, uint32_t *decay, int64_t plane,
+                                           int planes, int64_t words, int64_t nx, int64_t ny, int64_t W) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (int64_t)gridDim.x * blockDim.x) {
+        const WordAt at(i, W, ny);
+        const uint8_t *src = dense + ((size_t)at.u * (size_t)ny + (size_t)at.y) * (size_t)nx + 32 * at.j;
+        const int n = row_cells(nx, at.j);
+        uint32_t x = 0, d[4] = {0, 0, 0, 0};
+        for (int k = 0; k < n; ++k) {
+            const uint32_t s = src[k];
+            x |= (uint32_t)(s == 1u) << k;
+            const uint32_t e = s > 1u ? s - 1u : 0u;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) d[p] |= ((e >> p) & 1u) << k;
+        }
+        cells[i] = x;
+        for (int p = 0; p < planes; ++p) decay[(size_t)p * (size_t)plane + i] = d[p];
+    }
+}
+
+__global__ void batch_export_states_kernel(const uint32_t *cells, const uint32_t *decay, int64_t plane, int planes,
+                                           uint8_t *dense, int64_t words, int64_t nx, int64_t ny, int64_t W) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (int64_t)gridDim.x * blockDim.x) {
+        const WordAt at(i, W, ny);
+        uint8_t *dst = dense + ((size_t)at.u * (size_t)ny + (size_t)at.y) * (size_t)nx + 32 * at.j;
+        const int n = row_cells(nx, at.j);
+        const uint32_t x = cells[i];
+        uint32_t d[4] = {0, 0, 0, 0};
+        for (int p = 0; p < planes; ++p) d[p] = decay[(size_t)p * (size_t)plane + i];
+        for (int k = 0; k < n; ++k) {
+            const uint32_t e = plane_bits(d, k);
+            dst[k] = (uint8_t)(e ? e + 1u : (x >> k) & 1u);
+        }
+    }
+}
+
+// One wave per universe, as batch_census_kernel: s = 1 counted in live, s >= 2 in dying, s * cell_mix in sum.
+__global__ __launch_bounds__(64 * kBatchWaves) void batch_census_states_kernel(
+    const uint32_t *cells, const uint32_t *decay, int64_t plane, int planes, unsigned long long *live,
+    unsigned long long *dying, unsigned long long *sum, int64_t count, int64_t nx, int64_t ny, int64_t W) {
+    const int64_t u = (int64_t)blockIdx.x * kBatchWaves + (int64_t)(threadIdx.x >> 6);
+    if (u >= count) return;
+    const size_t uni = (size_t)u * (size_t)(W * ny);
+    const int64_t q = nx - 32 * (W - 1);
+    unsigned long long c = 0, dy = 0, x = 0;
+    for (int64_t i = threadIdx.x & 63u; i < W * ny; i += 64) {
+        const int64_t y = i / W, j = i % W;
+        const uint32_t keep = j == W - 1 && q < 32 ? (1u << q) - 1u : 0xFFFFFFFFu;  // (zero already beyond it)
+        const uint32_t alive = cells[uni + i] & keep;
+        uint32_t d[4] = {0, 0, 0, 0};
+        for (int p = 0; p < planes; ++p) d[p] = decay[(size_t)p * (size_t)plane + uni + i] & keep;
+        uint32_t bits = alive | d[0] | d[1] | d[2] | d[3];
+        c += __popc(alive);
+        dy += __popc(bits & ~alive);
+        const uint64_t base = (uint64_t)(y * nx + 32 * j) + 1u;
+        while (bits) {
+            const int b = __ffs(bits) - 1;
+            bits &= bits - 1u;
+            const uint32_t e = plane_bits(d, b);
+            x += (uint64_t)(e ? e + 1u : 1u) * cell_mix(base + (uint64_t)b);
+        }
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+        c += __shfl_xor(c, s);
+        dy += __shfl_xor(dy, s);
+        x += __shfl_xor(x, s);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        live[u] = c;
+        dying[u] = dy;
+        sum[u] = x;
+    }
+}
+
 unsigned word_blocks(int64_t words) { return (unsigned)std::min<int64_t>((words + 255) / 256, 1 << 20); }
 unsigned wave_blocks(int64_t count) { return (unsigned)((count + kBatchWaves - 1) / kBatchWaves); }
 // one workgroup per universe, or per kBatchWaves universes: the grid's x must hold them
@@ -533,6 +814,75 @@ hipError_t launch_batch_fill(const BatchPlan &p, int64_t nx, int64_t ny, int64_t
     const int64_t words = count * ny * p.words;
     if (words < 1) return hipSuccess;
     batch_fill_kernel<<<word_blocks(words), 256, 0, s>>>(cells, words, nx, ny, p.words, seed, thr32);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_gen(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, uint32_t *decay,
+                            int planes, int64_t gens, uint32_t birth, uint32_t survive, uint32_t states,
+                            const uint32_t *rules, bool settle, int64_t *settled, bool cycle, int64_t *period,
+                            int64_t *found, int64_t gen0, hipStream_t s) {
+    if (p.tier != LIFE_BATCH_TIER_WAVE || gens < 1 || gens > INT32_MAX || (settle && !settled) || (settle && cycle) ||
+        (cycle && (!period || !found)) || !decay || !grid_ok((count + kBatchWaves - 1) / kBatchWaves))
+        return hipErrorInvalidValue;
+    BNArgs a{};
+    a.cells = cells;
+    a.decay = decay;
+    a.plane = count * ny * p.words;
+    a.settled = settled;
+    a.count = count;
+    a.gen0 = gen0;
+    a.nx = (int32_t)nx;
+    a.ny = (int32_t)ny;
+    a.gens = (int32_t)gens;
+    a.birth = birth | states << 16;
+    a.survive = survive;
+    a.rules = reinterpret_cast<const uint2 *>(rules);
+    a.period = period;
+    a.found = found;
+    const int det = cycle ? kCycle : settle ? kSettle : kNoDetector;
+    const unsigned blocks = wave_blocks(count);
+    switch (p.words * 8 + planes) {
+#define LIFE_BN(N) \
+    case N * 8 + 1: return launch_gen<N, 1>(a, det, blocks, s); \
+    case N * 8 + 2: return launch_gen<N, 2>(a, det, blocks, s); \
+    case N * 8 + 4: return launch_gen<N, 4>(a, det, blocks, s);
+        LIFE_BN(1) LIFE_BN(2) LIFE_BN(3) LIFE_BN(4)
+#undef LIFE_BN
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_batch_import_states(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, int64_t first,
+                                      int64_t n, const uint8_t *dense, uint32_t *cells, uint32_t *decay, int planes,
+                                      hipStream_t s) {
+    const int64_t words = n * ny * p.words, skip = first * ny * p.words;
+    if (words < 1) return hipSuccess;
+    if (planes < 0 || planes > 4 || (planes && !decay)) return hipErrorInvalidValue;
+    batch_import_states_kernel<<<word_blocks(words), 256, 0, s>>>(dense, cells + skip, planes ? decay + skip : nullptr,
+                                                                  count * ny * p.words, planes, words, nx, ny, p.words);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_export_states(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, int64_t first,
+                                      int64_t n, const uint32_t *cells, const uint32_t *decay, int planes,
+                                      uint8_t *dense, hipStream_t s) {
+    const int64_t words = n * ny * p.words, skip = first * ny * p.words;
+    if (words < 1) return hipSuccess;
+    if (planes < 0 || planes > 4 || (planes && !decay)) return hipErrorInvalidValue;
+    batch_export_states_kernel<<<word_blocks(words), 256, 0, s>>>(cells + skip, planes ? decay + skip : nullptr,
+                                                                  count * ny * p.words, planes, dense, words, nx, ny,
+                                                                  p.words);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_census_states(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, const uint32_t *cells,
+                                      const uint32_t *decay, int planes, unsigned long long *live,
+                                      unsigned long long *dying, unsigned long long *sum, hipStream_t s) {
+    if (!grid_ok((count + kBatchWaves - 1) / kBatchWaves) || planes < 0 || planes > 4 || (planes && !decay))
+        return hipErrorInvalidValue;
+    batch_census_states_kernel<<<wave_blocks(count), 64 * kBatchWaves, 0, s>>>(cells, decay, count * ny * p.words,
+                                                                               planes, live, dying, sum, count, nx, ny,
+                                                                               p.words);
     return hipGetLastError();
 }
 

@@ -173,6 +173,16 @@ uint32_t conway7_host(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32
 // (at most 22 characters and the NUL).
 bool rule_parse(const char *text, uint32_t *birth, uint32_t *survive);
 void rule_format(uint32_t birth, uint32_t survive, char out[24]);
+// Generations rules (life_rule_parse_gen): the forms above
+// (states = 2), B2/S345/C4 (G for C, either letter case) and Golly's 345/2/4
+// (S/B/C); 2 <= states <= kGenMaxStates.  rule_format_gen appends /Cn where
+// states > 2 (at most 26 characters and the NUL).
+constexpr uint32_t kGenMaxStates = 16;
+bool rule_parse_gen(const char *text, uint32_t *birth, uint32_t *survive, uint32_t *states);
+void rule_format_gen(uint32_t birth, uint32_t survive, uint32_t states, char out[32]);
+// decay bit planes a universe of `states` states needs beside its alive plane:
+// d = s - 1 of a dying cell, at most states - 2 (the kernels are built for 1, 2 and 4)
+constexpr int gen_planes(uint32_t states) { return states <= 2 ? 0 : states <= 3 ? 1 : states <= 5 ? 2 : 4; }
 
 // Batches (life_batch_*): how `count` universes of one shape
 // are stored and launched.  Storage: natural 32-cell words, `words` per row,

@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "life_env.h"
@@ -439,6 +440,32 @@ void life::rule_format(uint32_t birth, uint32_t survive, char out[24]) {
     *p = '\0';
 }
 
+bool life::rule_parse_gen(const char *text, uint32_t *birth, uint32_t *survive, uint32_t *states) {
+    if (!text) return false;
+    const char *s1 = strchr(text, '/');
+    const char *s2 = s1 ? strchr(s1 + 1, '/') : nullptr;
+    if (!s2) {  // no third part: a Life-like rule
+        *states = 2;
+        return rule_parse(text, birth, survive);
+    }
+    // the first two parts are rule_parse's, the third the state count: one or two digits, no leading zero
+    const std::string head(text, (size_t)(s2 - text));
+    const char *p = s2 + 1;
+    if (*p == 'C' || *p == 'c' || *p == 'G' || *p == 'g') ++p;
+    if (*p < '1' || *p > '9') return false;
+    uint32_t c = (uint32_t)(*p++ - '0');
+    if (*p >= '0' && *p <= '9') c = 10 * c + (uint32_t)(*p++ - '0');
+    if (*p != '\0' || c < 2 || c > kGenMaxStates) return false;
+    if (!rule_parse(head.c_str(), birth, survive)) return false;
+    *states = c;
+    return true;
+}
+
+void life::rule_format_gen(uint32_t birth, uint32_t survive, uint32_t states, char out[32]) {
+    rule_format(birth, survive, out);
+    if (states > 2) snprintf(out + strlen(out), 8, "/C%u", states);
+}
+
 // life_last_error's setter lives with the device runtime (life_dev.hip); a
 // program that links this unit alone (the CPU harnesses) has none
 namespace life {
@@ -463,6 +490,26 @@ int life_rule_format(uint32_t birth, uint32_t survive, char out[24]) {
         return LIFE_EINVAL;
     }
     life::rule_format(birth, survive, out);
+    return LIFE_OK;
+}
+
+int life_rule_parse_gen(const char *text, uint32_t *birth, uint32_t *survive, uint32_t *states) {
+    if (birth && survive && states && life::rule_parse_gen(text, birth, survive, states)) return LIFE_OK;
+    if (life::rt::set_err)
+        life::rt::set_err("rule \"%.64s\": expected B<digits>/S<digits> or <digits>/<digits> (S/B), digits 0-8, with "
+                          "an optional third part /C<states> (G for C; S/B/<states>), states 2-%u",
+                          text ? text : "(null)", life::kGenMaxStates);
+    return LIFE_EINVAL;
+}
+
+int life_rule_format_gen(uint32_t birth, uint32_t survive, uint32_t states, char out[32]) {
+    if (!out || ((birth | survive) & ~life::kRuleMask) || states < 2 || states > life::kGenMaxStates) {
+        if (life::rt::set_err)
+            life::rt::set_err("rule masks 0x%x / 0x%x, %u states: bits above 8 or states outside 2-%u", birth, survive,
+                              states, life::kGenMaxStates);
+        return LIFE_EINVAL;
+    }
+    life::rule_format_gen(birth, survive, states, out);
     return LIFE_OK;
 }
 

@@ -85,7 +85,11 @@ ABI_SYMBOLS = (
     "life_batch_fill_random", "life_batch_set_rule", "life_batch_get_rule", "life_batch_configure",
     "life_batch_step", "life_batch_census", "life_batch_settled", "life_batch_generation", "life_batch_sync",
     "life_batch_set_rules", "life_batch_get_rules", "life_batch_cycles",
+    "life_rule_parse_gen", "life_rule_format_gen", "life_batch_set_rule_gen", "life_batch_get_rule_gen",
+    "life_batch_set_rules_gen", "life_batch_get_rules_gen", "life_batch_upload_states", "life_batch_gather_states",
+    "life_batch_census_gen",
 )
+GEN_MAX_STATES = 16  # LIFE_GEN_MAX_STATES
 BATCH_TIER_WAVE, BATCH_TIER_GROUP = 1, 2  # LIFE_BATCH_TIER_*
 BATCH_TIERS = {BATCH_TIER_WAVE: "wave", BATCH_TIER_GROUP: "group"}
 BATCH_OPT_SETTLE = 1  # LIFE_BATCH_OPT_SETTLE
@@ -226,6 +230,17 @@ def _lib():
             L.life_batch_set_rules.argtypes = [vp, i64, i64, P(u32), P(u32)]
             L.life_batch_get_rules.argtypes = [vp, i64, i64, P(u32), P(u32)]
             L.life_batch_cycles.argtypes = [vp, P(i64), P(i64)]
+        if hasattr(L, "life_batch_set_rule_gen"):  # absent from builds that predate Generations rules
+            u8 = ctypes.c_uint8
+            L.life_rule_parse_gen.argtypes = [ctypes.c_char_p, P(u32), P(u32), P(u32)]
+            L.life_rule_format_gen.argtypes = [u32, u32, u32, ctypes.c_char_p]
+            L.life_batch_set_rule_gen.argtypes = [vp, u32, u32, u32]
+            L.life_batch_get_rule_gen.argtypes = [vp, P(u32), P(u32), P(u32)]
+            L.life_batch_set_rules_gen.argtypes = [vp, i64, i64, P(u32), P(u32), P(u32)]
+            L.life_batch_get_rules_gen.argtypes = [vp, i64, i64, P(u32), P(u32), P(u32)]
+            L.life_batch_upload_states.argtypes = [vp, i64, i64, P(u8)]
+            L.life_batch_gather_states.argtypes = [vp, i64, i64, P(u8)]
+            L.life_batch_census_gen.argtypes = [vp, P(i64), P(i64), P(u64)]
         L.life_tune.argtypes = [i32, i32, i32]
         L.life_tune_temporal.argtypes = [i32, i32]
         L.life_measure_copy.argtypes = [i32, i64, i32, P(ctypes.c_double)]
@@ -322,9 +337,49 @@ def format_rule(birth: int, survive: int) -> str:
 def _rule_masks(rule):
     """A rulestring or a (birth, survive) pair -> the pair."""
     if isinstance(rule, str):
-        return parse_rule(rule)
+        try:
+            return parse_rule(rule)
+        except LifeError as e:
+            try:
+                states = parse_rule_gen(rule)[2]
+            except LifeError:
+                raise e from None
+            raise LifeError(e.rc, f"rule {rule!r} is a Generations rule of {states} states: those run on wave-tier "
+                                  "batches only (LifeBatch), not on Life") from None
     birth, survive = rule
     return int(birth), int(survive)
+
+
+def parse_rule_gen(text: str):
+    """(birth, survive, states) of a Generations rulestring (life_rule_parse_gen):
+    what :func:`parse_rule` accepts (states = 2), "B2/S345/C4" (G for C, either
+    letter case) and Golly's "345/2/4" (S/B/C), 2 <= states <= 16."""
+    b, s, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    _check(_lib().life_rule_parse_gen(str(text).encode(), ctypes.byref(b), ctypes.byref(s), ctypes.byref(c)),
+           "life_rule_parse_gen")
+    return b.value, s.value, c.value
+
+
+def format_rule_gen(birth: int, survive: int, states: int = 2) -> str:
+    """The canonical "B.../S.../Cn" (life_rule_format_gen); for two states
+    what :func:`format_rule` gives."""
+    if not all(0 <= int(v) < 2**32 for v in (birth, survive, states)):
+        raise ValueError(f"rule masks {birth}, {survive} or state count {states} are not 32-bit")
+    out = ctypes.create_string_buffer(32)
+    _check(_lib().life_rule_format_gen(int(birth), int(survive), int(states), out), "life_rule_format_gen")
+    return out.value.decode()
+
+
+def _rule_triple(rule):
+    """A rulestring, a (birth, survive) pair or a (birth, survive, states)
+    triple -> the triple (a pair has two states)."""
+    if isinstance(rule, str):
+        return parse_rule_gen(rule)
+    rule = tuple(int(v) for v in rule)
+    if len(rule) == 2:
+        return rule + (2,)
+    birth, survive, states = rule
+    return birth, survive, states
 
 
 def batch_query(nx: int, ny: int):
@@ -678,7 +733,9 @@ class LifeBatch:
     Every call is ordered on the batch's one stream: ``step`` returns at once,
     and a following ``gather`` / ``live_counts`` / ``checksums`` / ``settled``
     waits for it.  ``rule``: None (B3/S23), a rulestring or a (birth, survive)
-    pair (wave tier only).  ``rules``: one such rule per universe
+    pair (wave tier only); a Generations rule ("B2/S/C3", a (birth, survive,
+    states) triple) gives every cell up to 16 states, moved by
+    :meth:`upload_states` / :meth:`gather_states`.  ``rules``: one such rule per universe
     (:meth:`set_rules`; wave tier only).  ``settle``: stop a universe early once
     it repeats with period 1 or 2 (LIFE_BATCH_OPT_SETTLE; wave tier only).
     ``cycle``: find cycles of any period instead (LIFE_BATCH_OPT_CYCLE,
@@ -704,35 +761,50 @@ class LifeBatch:
         _check(_lib().life_batch_configure(self._h, int(option), int(value)), "life_batch_configure")
 
     def set_rule(self, rule) -> None:
-        """life_batch_set_rule: what :meth:`Life.set_rule` accepts; a rule other
-        than B3/S23 needs a wave-tier batch.  Clears every settled flag."""
-        birth, survive = _rule_masks(rule)
-        if not (0 <= birth < 2**32 and 0 <= survive < 2**32):
-            raise ValueError(f"rule masks {birth}, {survive} are not 32-bit")
-        _check(_lib().life_batch_set_rule(self._h, birth, survive), "life_batch_set_rule")
+        """life_batch_set_rule: what :meth:`Life.set_rule` accepts, and
+        Generations rules ("B2/S/C3", a (birth, survive, states) triple: life_
+        batch_set_rule_gen); a rule other than B3/S23 needs a wave-tier batch.
+        Clears every settled flag and resets every dying cell to dead."""
+        birth, survive, states = _rule_triple(rule)
+        if not all(0 <= v < 2**32 for v in (birth, survive, states)):
+            raise ValueError(f"rule masks {birth}, {survive} or state count {states} are not 32-bit")
+        if states > 2:
+            _check(_lib().life_batch_set_rule_gen(self._h, birth, survive, states), "life_batch_set_rule_gen")
+        else:
+            _check(_lib().life_batch_set_rule(self._h, birth, survive), "life_batch_set_rule")
 
     @property
     def rule(self) -> str:
-        """The one rule of a uniform batch; LifeError (LIFE_ESTATE) once
-        :meth:`set_rules` gave the universes rules of their own (see ``rules``)."""
-        b, s = ctypes.c_uint32(), ctypes.c_uint32()
-        _check(_lib().life_batch_get_rule(self._h, ctypes.byref(b), ctypes.byref(s)), "life_batch_get_rule")
-        return format_rule(b.value, s.value)
+        """The one rule of a uniform batch, with /Cn where it has more than two
+        states; LifeError (LIFE_ESTATE) once :meth:`set_rules` gave the
+        universes rules of their own (see ``rules``)."""
+        b, s, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        _check(_lib().life_batch_get_rule_gen(self._h, ctypes.byref(b), ctypes.byref(s), ctypes.byref(c)),
+               "life_batch_get_rule_gen")
+        return format_rule_gen(b.value, s.value, c.value)
 
     def set_rules(self, rules, first: int = 0) -> None:
         """life_batch_set_rules: universes [first, first + len(rules)) take
-        ``rules``, a sequence of rulestrings or (birth, survive) pairs; the
-        others keep theirs.  Clears the settled and cycle flags of those
-        universes.  The batch steps a rule per universe until :meth:`set_rule`."""
-        masks = [_rule_masks(r) for r in rules]
-        for birth, survive in masks:
-            if not (0 <= birth < 2**32 and 0 <= survive < 2**32):
-                raise ValueError(f"rule masks {birth}, {survive} are not 32-bit")
+        ``rules``, a sequence of rulestrings, (birth, survive) pairs or (birth,
+        survive, states) triples; the others keep theirs.  Clears the settled and
+        cycle flags of those universes and resets their dying cells to dead.
+        The batch steps a rule per universe until :meth:`set_rule`.  Where an
+        entry has more than two states the call is life_batch_set_rules_gen."""
+        masks = [_rule_triple(r) for r in rules]
+        for birth, survive, states in masks:
+            if not all(0 <= v < 2**32 for v in (birth, survive, states)):
+                raise ValueError(f"rule masks {birth}, {survive} or state count {states} are not 32-bit")
         birth = np.array([m[0] for m in masks], dtype=np.uint32)
         survive = np.array([m[1] for m in masks], dtype=np.uint32)
+        states = np.array([m[2] for m in masks], dtype=np.uint32)
         u32p = ctypes.POINTER(ctypes.c_uint32)
-        _check(_lib().life_batch_set_rules(self._h, int(first), len(masks), birth.ctypes.data_as(u32p),
-                                           survive.ctypes.data_as(u32p)), "life_batch_set_rules")
+        if (states > 2).any():
+            _check(_lib().life_batch_set_rules_gen(self._h, int(first), len(masks), birth.ctypes.data_as(u32p),
+                                                   survive.ctypes.data_as(u32p), states.ctypes.data_as(u32p)),
+                   "life_batch_set_rules_gen")
+        else:
+            _check(_lib().life_batch_set_rules(self._h, int(first), len(masks), birth.ctypes.data_as(u32p),
+                                               survive.ctypes.data_as(u32p)), "life_batch_set_rules")
 
     def rule_masks(self, first: int = 0, n: int | None = None):
         """(birth, survive) uint32 arrays of universes [first, first + n)
@@ -745,10 +817,28 @@ class LifeBatch:
                                            survive.ctypes.data_as(u32p)), "life_batch_get_rules")
         return birth, survive
 
+    def rule_triples(self, first: int = 0, n: int | None = None):
+        """(birth, survive, states) uint32 arrays of universes [first, first +
+        n) (life_batch_get_rules_gen; n None: all from `first` on)."""
+        first = int(first)
+        n = self.count - first if n is None else int(n)
+        birth, survive, states = (np.zeros(max(n, 0), dtype=np.uint32) for _ in range(3))
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        _check(_lib().life_batch_get_rules_gen(self._h, first, n, birth.ctypes.data_as(u32p),
+                                               survive.ctypes.data_as(u32p), states.ctypes.data_as(u32p)),
+               "life_batch_get_rules_gen")
+        return birth, survive, states
+
     @property
     def rules(self) -> list:
-        """The canonical rulestring of every universe."""
-        return [format_rule(int(b), int(s)) for b, s in zip(*self.rule_masks())]
+        """The canonical rulestring of every universe (with /Cn where it has
+        more than two states)."""
+        return [format_rule_gen(int(b), int(s), int(c)) for b, s, c in zip(*self.rule_triples())]
+
+    @property
+    def states(self) -> np.ndarray:
+        """The state count of every universe (uint32, count entries)."""
+        return self.rule_triples()[2]
 
     @property
     def generation(self) -> int:
@@ -776,9 +866,54 @@ class LifeBatch:
                "life_batch_gather")
         return out
 
+    def upload_states(self, grids, first: int = 0) -> None:
+        """Universes [first, first + n) from an (n, ny, nx) array of cell states
+        (0 dead, 1 alive, 2 .. C - 1 dying; life_batch_upload_states): every value
+        must be below the state count of its universe."""
+        g = np.asarray(grids)
+        if g.ndim != 3 or g.shape[1:] != (self.ny, self.nx):
+            raise ValueError(f"upload_states: grids shape {g.shape} != (n, {self.ny}, {self.nx})")
+        if g.size and (g.min() < 0 or g.max() > 255):
+            raise ValueError("upload_states: cell states are 0 .. 255")
+        g = np.ascontiguousarray(g, dtype=np.uint8)
+        _check(_lib().life_batch_upload_states(self._h, int(first), g.shape[0],
+                                               g.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+               "life_batch_upload_states")
+
+    def gather_states(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """Universes [first, first + n) as an (n, ny, nx) uint8 array of cell
+        states (n None: all from `first` on)."""
+        first = int(first)
+        n = self.count - first if n is None else int(n)
+        out = _host_buffer((max(n, 0), self.ny, self.nx))
+        _check(_lib().life_batch_gather_states(self._h, first, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+               "life_batch_gather_states")
+        return out
+
+    def census_gen(self):
+        """(live, dying, checksum) of every universe (life_batch_census_gen):
+        the cells in state 1, the cells in states >= 2 (int64), and the sum of
+        state x mix64(y nx + x + 1) over all cells modulo 2^64 (uint64)."""
+        live, dying = np.zeros(self.count, dtype=np.int64), np.zeros(self.count, dtype=np.int64)
+        sums = np.zeros(self.count, dtype=np.uint64)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        _check(_lib().life_batch_census_gen(self._h, live.ctypes.data_as(i64p), dying.ctypes.data_as(i64p),
+                                            sums.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))),
+               "life_batch_census_gen")
+        return live, dying, sums
+
+    def dying_counts(self) -> np.ndarray:
+        """The dying cells (state >= 2) of every universe (int64, count entries)."""
+        return self.census_gen()[1]
+
+    def state_checksums(self) -> np.ndarray:
+        """The checksum over the whole state of every universe (uint64): equal
+        to :meth:`checksums` where nothing is dying."""
+        return self.census_gen()[2]
+
     def fill_random(self, seed: int, density: float = 0.5) -> None:
         """Universe u becomes what ``Life.fill_random(seed + u, density)`` gives
-        an nx x ny grid (seed + u modulo 2^64)."""
+        an nx x ny grid (seed + u modulo 2^64); nothing is dying."""
         _check(_lib().life_batch_fill_random(self._h, int(seed) % 2**64, density_to_thr(density)),
                "life_batch_fill_random")
 

@@ -20,7 +20,16 @@ line's batch (16384 soups of 32 x 32 at 35 %, step(4096)) with detection off,
 settle on and cycle on, and the share of universes each detector found.
 
     python scripts/batch_bench.py --out profiles/batch/batch_bench.jsonl
+The Generations lines, reported and not gated: 262144
+universes of 64 x 64, 50 % soups (fill_random: nothing dying at the start),
+step(1024) under Brian's Brain (one decay plane), Star Wars (two), a rule of 16
+states (four) and, in the same run, uniform HighLife on the two-state table
+kernel as the yardstick; then one line with a (rule, C) per universe, the four
+rules in turn.
+
+    python scripts/batch_bench.py --out profiles/batch/batch_bench.jsonl
     python scripts/batch_bench.py --only survey --out profiles/batch/survey_bench.jsonl
+    python scripts/batch_bench.py --only gen --out profiles/batch/gen_bench.jsonl
 """
 import argparse
 import json
@@ -49,16 +58,20 @@ def timed(fn, sync):
 
 def batch_time(nx, ny, count, gens, reps, density=0.5, settle=False, rule=None, rules=None, cycle=False):
     """(median s, min s, max s, share of universes the detector found, checksums)
-    of LifeBatch.step(gens); rules: one rule for every universe, through set_rules."""
+    of LifeBatch.step(gens); rules: one rule for every universe, through set_rules,
+    or a list of rules taken in turn.  Checksums: over the whole state."""
     with lm.LifeBatch(nx, ny, count, settle=settle, rule=rule, cycle=cycle) as b:
-        if rules is not None:
+        if isinstance(rules, (list, tuple)):
+            triples = [lm.parse_rule_gen(r) for r in rules]
+            b.set_rules([triples[u % len(triples)] for u in range(count)])
+        elif rules is not None:
             b.set_rules([lm.parse_rule(rules)] * count)
         times = []
         for rep in range(reps + 1):  # the first is the warm-up
             b.fill_random(SEED, density)
             times.append(timed(lambda: b.step(gens), b.sync))
         share = float((b.settled() >= 0).mean()) if settle else float((b.cycles()[0] > 0).mean()) if cycle else 0.0
-        sums = b.checksums()
+        sums = b.state_checksums() if (b.states > 2).any() else b.checksums()
     t = times[1:]
     return statistics.median(t), min(t), max(t), share, sums
 
@@ -100,8 +113,8 @@ def main():
     ap.add_argument("--settle-gens", type=int, default=4096)
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="the smallest count of every shape only")
-    ap.add_argument("--only", choices=("all", "table", "settle", "survey"), default="all",
-                    help="the shape table, the settle line or the survey lines alone")
+    ap.add_argument("--only", choices=("all", "table", "settle", "survey", "gen"), default="all",
+                    help="the shape table, the settle line, the survey lines or the Generations lines alone")
     a = ap.parse_args()
     out = open(a.out, "w") if a.out else None
 
@@ -162,6 +175,25 @@ def main():
               "per_universe_min_s": per[1], "per_universe_max_s": per[2], "per_universe_over_uniform": per[0] / uni[0],
               "uniform_tcups": nx * ny * count * a.gens / uni[0] / 1e12,
               "per_universe_tcups": nx * ny * count * a.gens / per[0] / 1e12})
+    if a.only in ("all", "gen"):
+        # Generations: the uniform two-state table kernel of the same run is the yardstick
+        nx, ny, count = 64, 64, 1024 if a.quick else 262144
+        updates = nx * ny * count * a.gens
+        yard = batch_time(nx, ny, count, a.gens, a.reps, rule="B36/S23")
+        emit({"generations": True, "shape": [nx, ny], "count": count, "gens": a.gens, "rule": "B36/S23", "planes": 0,
+              "s": yard[0], "min_s": yard[1], "max_s": yard[2], "tcups": updates / yard[0] / 1e12,
+              "over_highlife": 1.0})
+        named = [("B2/S/C3", 1), ("B2/S345/C4", 2), ("B2/S345/C16", 4)]
+        for rule, planes in named:
+            t = batch_time(nx, ny, count, a.gens, a.reps, rule=rule)
+            emit({"generations": True, "shape": [nx, ny], "count": count, "gens": a.gens, "rule": rule,
+                  "planes": planes, "s": t[0], "min_s": t[1], "max_s": t[2], "tcups": updates / t[0] / 1e12,
+                  "over_highlife": t[0] / yard[0]})
+        mix = [r for r, _ in named] + ["B36/S23"]
+        t = batch_time(nx, ny, count, a.gens, a.reps, rules=mix)
+        emit({"generations": True, "shape": [nx, ny], "count": count, "gens": a.gens, "rule": "per universe",
+              "rules": mix, "planes": 4, "s": t[0], "min_s": t[1], "max_s": t[2], "tcups": updates / t[0] / 1e12,
+              "over_highlife": t[0] / yard[0]})
     print("| shape | count | batch ms | host loop ms (scaled) | ratio | Tcell-updates/s |", file=sys.stderr)
     print("|---|---|---|---|---|---|", file=sys.stderr)
     for r in table:
