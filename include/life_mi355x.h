@@ -655,6 +655,15 @@ typedef struct life_batch life_batch; /* opaque: device memory and one stream */
  * takes on the device, 4 * ceil(nx/32) * ny.  Either out pointer may be NULL.
  * LIFE_EINVAL with a message for a shape in neither tier. */
 int life_batch_query(int64_t nx, int64_t ny, int *tier, int64_t *bytes_per_universe);
+/* Host only: the rest of the plan of a shape, that is which kernel instance
+ * and launch life_batch_step takes.  words: 32-cell words per row, ceil(nx/32);
+ * threads: threads of a workgroup, 64 * its waves.  Group tier:
+ * lanes_per_strip = Wp, `words` rounded up to a power of two; rows = the strip
+ * height R; strips = ny / R (strips * lanes_per_strip of the threads own
+ * words).  Wave tier: lanes_per_strip, rows and strips are 0.  Any out pointer
+ * may be NULL.  Refuses what life_batch_query refuses, with the same message. */
+int life_batch_query_plan(int64_t nx, int64_t ny, int *tier, int *words, int *lanes_per_strip, int *rows, int *strips,
+                          int *threads);
 /* count >= 1 universes, all dead, on HIP device `device`, rule B3/S23,
  * generation 0.  Blocking.  LIFE_EINVAL: the shape (as life_batch_query), count
  * < 1, out NULL; LIFE_EHIP: no such device; LIFE_ENOMEM. */

@@ -524,6 +524,23 @@ int life_batch_query(int64_t nx, int64_t ny, int *tier, int64_t *bytes_per_unive
     return LIFE_OK;
 }
 
+int life_batch_query_plan(int64_t nx, int64_t ny, int *tier, int *words, int *lanes_per_strip, int *rows, int *strips,
+                          int *threads) {
+    const life::BatchPlan p = life::batch_plan(nx, ny);
+    if (p.tier == 0) {
+        if (life::rt::set_err) life::rt::set_err("%s", p.why);
+        return LIFE_EINVAL;
+    }
+    const bool group = p.tier == LIFE_BATCH_TIER_GROUP;
+    if (tier) *tier = p.tier;
+    if (words) *words = p.words;
+    if (lanes_per_strip) *lanes_per_strip = group ? 1 << p.lg_wp : 0;
+    if (rows) *rows = group ? p.rows : 0;
+    if (strips) *strips = group ? p.strips : 0;
+    if (threads) *threads = 64 * p.waves_per_group;
+    return LIFE_OK;
+}
+
 }  // extern "C"
 
 // ---- batches (life_host.h)
@@ -540,9 +557,9 @@ life::BatchPlan life::batch_plan(int64_t nx, int64_t ny) {
     if (nx < 1 || ny < 1) return fail("empty shape");
     if (nx > kBatchGroupMaxX) return fail("too wide");
     p.words = (int)((nx + 31) / 32);
-    p.bytes = 4 * (int64_t)p.words * ny;
     if (nx <= kBatchWaveMaxX && ny <= kBatchWaveMaxY) {
         p.tier = LIFE_BATCH_TIER_WAVE;
+        p.bytes = 4 * (int64_t)p.words * ny;
         p.waves_per_group = kBatchWaves;
         p.universes_per_group = kBatchWaves;
         return p;
@@ -553,6 +570,7 @@ life::BatchPlan life::batch_plan(int64_t nx, int64_t ny) {
     for (int R : kRows)
         if (ny % R == 0 && ny / R <= strips) {
             p.tier = LIFE_BATCH_TIER_GROUP;
+            p.bytes = 4 * (int64_t)p.words * ny;  // of an accepted shape only: ny is any int64 before this
             p.rows = R;
             p.strips = (int)(ny / R);
             p.waves_per_group = (int)((((int64_t)p.strips << p.lg_wp) + 63) / 64);
@@ -560,7 +578,6 @@ life::BatchPlan life::batch_plan(int64_t nx, int64_t ny) {
             return p;
         }
     p.words = 0;
-    p.bytes = 0;
     return fail("no strip height fits one workgroup");
 }
 

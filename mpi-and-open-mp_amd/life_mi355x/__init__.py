@@ -22,6 +22,7 @@ no HIP device is present.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import importlib.abc
 import os
@@ -87,7 +88,7 @@ ABI_SYMBOLS = (
     "life_batch_set_rules", "life_batch_get_rules", "life_batch_cycles",
     "life_rule_parse_gen", "life_rule_format_gen", "life_batch_set_rule_gen", "life_batch_get_rule_gen",
     "life_batch_set_rules_gen", "life_batch_get_rules_gen", "life_batch_upload_states", "life_batch_gather_states",
-    "life_batch_census_gen",
+    "life_batch_census_gen", "life_batch_query_plan",
 )
 GEN_MAX_STATES = 16  # LIFE_GEN_MAX_STATES
 BATCH_TIER_WAVE, BATCH_TIER_GROUP = 1, 2  # LIFE_BATCH_TIER_*
@@ -241,6 +242,8 @@ def _lib():
             L.life_batch_upload_states.argtypes = [vp, i64, i64, P(u8)]
             L.life_batch_gather_states.argtypes = [vp, i64, i64, P(u8)]
             L.life_batch_census_gen.argtypes = [vp, P(i64), P(i64), P(u64)]
+        if hasattr(L, "life_batch_query_plan"):  # absent from builds that predate it
+            L.life_batch_query_plan.argtypes = [i64, i64] + [P(ctypes.c_int)] * 6
         L.life_tune.argtypes = [i32, i32, i32]
         L.life_tune_temporal.argtypes = [i32, i32]
         L.life_measure_copy.argtypes = [i32, i64, i32, P(ctypes.c_double)]
@@ -390,6 +393,21 @@ def batch_query(nx: int, ny: int):
     tier, nbytes = ctypes.c_int(), ctypes.c_int64()
     _check(_lib().life_batch_query(int(nx), int(ny), ctypes.byref(tier), ctypes.byref(nbytes)), "life_batch_query")
     return BATCH_TIERS[tier.value], nbytes.value
+
+
+BatchPlan = collections.namedtuple("BatchPlan", "tier words lanes_per_strip rows strips threads")
+
+
+def batch_plan(nx: int, ny: int) -> BatchPlan:
+    """The kernel instance and launch of a batch of nx x ny universes
+    (life_batch_query_plan, no GPU needed): ``tier`` as :func:`batch_query`,
+    ``words`` per row, ``threads`` of a workgroup, and on the group tier the
+    ``lanes_per_strip`` (``words`` rounded up to a power of two), the strip
+    height ``rows`` and the ``strips`` = ny / rows of a universe (0 on the wave
+    tier); LifeError for a shape in neither."""
+    out = [ctypes.c_int() for _ in range(6)]
+    _check(_lib().life_batch_query_plan(int(nx), int(ny), *map(ctypes.byref, out)), "life_batch_query_plan")
+    return BatchPlan(BATCH_TIERS[out[0].value], *(v.value for v in out[1:]))
 
 
 def density_to_thr(density: float) -> int:
