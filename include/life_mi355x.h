@@ -647,7 +647,8 @@ void life_dev_destroy(life_dev *d);
  *                         5 6 8 10 12 16 20 25 32, at most 1024 / Wp strips,
  *                         Wp = the words per row rounded up to a power of
  *                         two): one universe per workgroup, B3/S23 only.
- * Any other shape is LIFE_EINVAL, with a message naming both limits. */
+ * Any other shape is LIFE_EINVAL, with a message naming both limits.  Both
+ * tiers take LIFE_BATCH_OPT_POPULATION. */
 typedef struct life_batch life_batch; /* opaque: device memory and one stream */
 #define LIFE_BATCH_TIER_WAVE 1
 #define LIFE_BATCH_TIER_GROUP 2
@@ -784,9 +785,26 @@ int life_batch_census_gen(life_batch *b, int64_t *live, int64_t *dying, uint64_t
  * step(255) and not by step(100) + step(155)).  life_batch_settled is not
  * touched by this option.  LIFE_EINVAL: a group-tier batch, a value other
  * than 0 / 1, turning it on while LIFE_BATCH_OPT_SETTLE is on.
+ * LIFE_BATCH_OPT_POPULATION (both tiers, value 0 / 1, default 0): while on,
+ * every life_batch_step(b, n) records, for every universe, the live cells
+ * after each of the call's n generations (life_batch_population), in the
+ * kernels that hold the universes: the call stays one asynchronous launch and
+ * nothing is read back during it.  The states, census, settled flags and
+ * cycle pairs it leaves are bit-identical with the option on and off; with a
+ * detector on, a wave computes all n generations instead of leaving early, so
+ * the trace is complete for every universe.  A recording call holds count x n
+ * entries of 4 bytes on the device, in a buffer allocated on first need, grown
+ * to the largest call and released by life_batch_destroy and by turning the
+ * option off.  A call of more than 2^30 entries (4 GiB) is refused with
+ * LIFE_EINVAL before anything is allocated or launched, with the states and
+ * the generation counter unchanged: split the call.  Two-state universes
+ * only: LIFE_EINVAL when turned on while a universe's rule has more than two
+ * states, and from life_batch_set_rule_gen / _set_rules_gen with more than
+ * two states while it is on (their two-state calls keep working).
  * Option number 2 is unassigned and stays LIFE_EINVAL. */
 #define LIFE_BATCH_OPT_SETTLE 1
 #define LIFE_BATCH_OPT_CYCLE 3
+#define LIFE_BATCH_OPT_POPULATION 4
 int life_batch_configure(life_batch *b, int option, int value);
 /* All universes advance `generations`.  Asynchronous (one launch); 0 is a
  * no-op; LIFE_EINVAL when negative or above INT32_MAX. */
@@ -805,6 +823,16 @@ int life_batch_settled(life_batch *b, int64_t *generation);
  * upload or a life_batch_set_rules range that covers it, all of them with
  * life_batch_fill_random and life_batch_set_rule.  Blocking. */
 int life_batch_cycles(life_batch *b, int64_t *period, int64_t *generation);
+/* The population trace of LIFE_BATCH_OPT_POPULATION.  *generations (may be
+ * NULL) is the number G of generations the last life_batch_step call
+ * recorded: its n with the option on; 0 with the option off, for a call of 0
+ * generations, and before any call.  counts[(u - first) * G + g] is the live
+ * cells of universe u, first <= u < first + n, after generation g + 1 of that
+ * call; counts == NULL only queries G.  Range errors are those of
+ * life_batch_gather.  The trace stays readable until the next step call or
+ * until the option is turned off: uploads, fills and rule changes do not
+ * touch it.  Blocking. */
+int life_batch_population(life_batch *b, int64_t first, int64_t n, uint32_t *counts, int64_t *generations);
 /* Generations stepped since the states were last written as a whole
  * (creation, life_batch_fill_random, an upload of all universes).  Host only. */
 int life_batch_generation(life_batch *b, int64_t *generation);

@@ -43,6 +43,11 @@ struct life_batch {
     uint32_t *decay = nullptr;
     int planes = 0;
     unsigned long long *census_gen = nullptr;  // live[count], dying[count], checksum[count] of life_batch_census_gen
+    // LIFE_BATCH_OPT_POPULATION: the trace of the last step call, count * trace_gens entries,
+    // universe-major, in a buffer of trace_cap entries (grown to the largest call, released with the option)
+    bool population = false;
+    uint32_t *trace = nullptr;
+    int64_t trace_cap = 0, trace_gens = 0;
 };
 
 namespace {
@@ -145,6 +150,33 @@ int rule_ok(uint32_t birth, uint32_t survive, int64_t at, const char *call = "li
     return LIFE_OK;
 }
 
+// the trace buffer is released (the stream may still write it)
+int drop_trace(life_batch *b) {
+    b->trace_gens = 0;
+    if (!b->trace) return LIFE_OK;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(hipFree(b->trace));
+    b->trace = nullptr;
+    b->trace_cap = 0;
+    return LIFE_OK;
+}
+
+// at least `entries` entries of trace; what an older buffer held is lost
+int grow_trace(life_batch *b, int64_t entries) {
+    if (b->trace_cap >= entries) return LIFE_OK;
+    CHK(drop_trace(b));
+    HIPCHK(hipMalloc(&b->trace, sizeof(uint32_t) * (size_t)entries));
+    b->trace_cap = entries;
+    return LIFE_OK;
+}
+
+// a rule of more than two states while LIFE_BATCH_OPT_POPULATION is on
+int population_refuses(const char *call) {
+    set_err("%s: LIFE_BATCH_OPT_POPULATION is on, and a population trace counts two-state universes only (turn it "
+            "off before a Generations rule)", call);
+    return LIFE_EINVAL;
+}
+
 // the table of a mixed batch is released: the batch is uniform again
 int drop_rules(life_batch *b) {
     b->shadow.clear();
@@ -163,6 +195,7 @@ void free_batch(life_batch *b) {
     if (b->rules) (void)hipFree(b->rules);
     if (b->cycles) (void)hipFree(b->cycles);
     if (b->decay) (void)hipFree(b->decay);
+    if (b->trace) (void)hipFree(b->trace);
     if (b->census) (void)hipFree(b->census);
     if (b->census_gen) (void)hipFree(b->census_gen);
     if (b->stage) (void)hipFree(b->stage);
@@ -234,6 +267,7 @@ int set_rules(life_batch *b, int64_t first, int64_t n, const uint32_t *birth, co
             return LIFE_EINVAL;
         }
     }
+    if (most > 2 && b->population) return population_refuses(call);
     HIPCHK(hipSetDevice(b->device));
     if (wave) {
         CHK(grow_decay(b, life::gen_planes(most)));
@@ -437,6 +471,7 @@ int life_batch_set_rule_gen(life_batch *b, uint32_t birth, uint32_t survive, uin
     CHK(rule_ok(birth, survive, -1));
     CHK(states_ok(b, birth, survive, states, -1, "life_batch_set_rule_gen"));
     if (states == 2) return life_batch_set_rule(b, birth, survive);
+    if (b->population) return population_refuses("life_batch_set_rule_gen");
     HIPCHK(hipSetDevice(b->device));
     CHK(grow_decay(b, life::gen_planes(states)));
     CHK(drop_rules(b));
@@ -542,9 +577,24 @@ int life_batch_census_gen(life_batch *b, int64_t *live, int64_t *dying, uint64_t
 int life_batch_configure(life_batch *b, int option, int value) {
     if (!b) return LIFE_EINVAL;
     // (option 2 is unassigned)
-    if ((option != LIFE_BATCH_OPT_SETTLE && option != LIFE_BATCH_OPT_CYCLE) || (value != 0 && value != 1)) {
+    if ((option != LIFE_BATCH_OPT_SETTLE && option != LIFE_BATCH_OPT_CYCLE && option != LIFE_BATCH_OPT_POPULATION) ||
+        (value != 0 && value != 1)) {
         set_err("life_batch_configure: option %d value %d", option, value);
         return LIFE_EINVAL;
+    }
+    if (option == LIFE_BATCH_OPT_POPULATION) {  // both tiers
+        if (value && max_states(b) > 2) {
+            set_err("LIFE_BATCH_OPT_POPULATION: the batch runs a Generations rule of %u states (life_batch_set_rule_gen "
+                    "/ life_batch_set_rules_gen), and a population trace counts two-state universes only",
+                    max_states(b));
+            return LIFE_EINVAL;
+        }
+        if (!value) {
+            HIPCHK(hipSetDevice(b->device));
+            CHK(drop_trace(b));
+        }
+        b->population = value != 0;
+        return LIFE_OK;
     }
     const bool settle = option == LIFE_BATCH_OPT_SETTLE;
     const char *name = settle ? "LIFE_BATCH_OPT_SETTLE" : "LIFE_BATCH_OPT_CYCLE";
@@ -580,10 +630,31 @@ int life_batch_step(life_batch *b, int64_t generations) {
         set_err("life_batch_step: %lld generations (0 .. %d)", (long long)generations, INT32_MAX);
         return LIFE_EINVAL;
     }
-    if (generations == 0) return LIFE_OK;
+    if (b->population && generations > life::kBatchTraceEntries / b->count) {
+        set_err("life_batch_step: LIFE_BATCH_OPT_POPULATION would record %lld universes x %lld generations, more than "
+                "%lld entries: split the call", (long long)b->count, (long long)generations,
+                (long long)life::kBatchTraceEntries);
+        return LIFE_EINVAL;
+    }
+    if (generations == 0) {
+        b->trace_gens = 0;  // (a call that recorded nothing)
+        return LIFE_OK;
+    }
     HIPCHK(hipSetDevice(b->device));
     const uint32_t most = max_states(b);
-    if (most > 2)  // (wave tier: no other takes such a rule)
+    int64_t *const found = b->cycles ? b->cycles + b->count : nullptr;
+    if (b->population) {  // (two-state: the option and the Generations rules refuse each other)
+        CHK(grow_trace(b, b->count * generations));
+        b->trace_gens = 0;
+        if (b->plan.tier == LIFE_BATCH_TIER_WAVE)
+            HIPCHK(life::launch_batch_trace(b->plan, b->nx, b->ny, b->count, b->cells, generations,
+                                            b->table ? &b->words : nullptr, b->rules, b->settle, b->settled, b->cycle,
+                                            b->cycles, found, b->generation, b->trace, b->stream));
+        else
+            HIPCHK(life::launch_batch_group_trace(b->plan, b->nx, b->ny, b->count, b->cells, generations, b->trace,
+                                                  b->stream));
+        b->trace_gens = generations;
+    } else if (most > 2)  // (wave tier: no other takes such a rule)
         HIPCHK(life::launch_batch_gen(b->plan, b->nx, b->ny, b->count, b->cells, b->decay, life::gen_planes(most),
                                       generations, b->birth, b->survive, b->states, b->rules, b->settle, b->settled,
                                       b->cycle, b->cycles, b->cycles ? b->cycles + b->count : nullptr, b->generation,
@@ -615,6 +686,19 @@ int life_batch_census(life_batch *b, int64_t *live, uint64_t *checksum) {
     const size_t bytes = sizeof(unsigned long long) * (size_t)b->count;
     if (live) HIPCHK(hipMemcpyAsync(live, d_live, bytes, hipMemcpyDeviceToHost, b->stream));
     if (checksum) HIPCHK(hipMemcpyAsync(checksum, d_sum, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+int life_batch_population(life_batch *b, int64_t first, int64_t n, uint32_t *counts, int64_t *generations) {
+    if (!b) return LIFE_EINVAL;
+    CHK(range_ok(b, first, n, b, "life_batch_population"));
+    const int64_t gens = b->population ? b->trace_gens : 0;
+    if (generations) *generations = gens;
+    if (!counts || n == 0 || gens == 0) return LIFE_OK;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipMemcpyAsync(counts, b->trace + (size_t)first * (size_t)gens, sizeof(uint32_t) * (size_t)(n * gens),
+                          hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return LIFE_OK;
 }

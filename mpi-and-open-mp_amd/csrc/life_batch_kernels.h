@@ -42,6 +42,19 @@ hipError_t launch_batch_gen(const BatchPlan &p, int64_t nx, int64_t ny, int64_t 
 // Group tier (B3/S23): one workgroup per universe.
 hipError_t launch_batch_group(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
                               int64_t gens, hipStream_t s);
+// The recording forms of LIFE_BATCH_OPT_POPULATION, kernels of
+// their own beside the ones above: the same call, and trace[u * gens + g] = the
+// live cells of universe u after generation g + 1 of it, for every universe
+// and generation whatever a detector does (the wave runs on).  `trace` holds
+// count * gens entries, at most kBatchTraceEntries.  launch_batch_trace serves
+// every two-state form of the wave tier (arguments as launch_batch_survey, but
+// rules and cycle may both be unset), launch_batch_group_trace the group tier.
+constexpr int64_t kBatchTraceEntries = (int64_t)1 << 30;
+hipError_t launch_batch_trace(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
+                              const RuleWords *rule, const uint32_t *rules, bool settle, int64_t *settled, bool cycle,
+                              int64_t *period, int64_t *found, int64_t gen0, uint32_t *trace, hipStream_t s);
+hipError_t launch_batch_group_trace(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
+                                    int64_t gens, uint32_t *trace, hipStream_t s);
 // live[u] / sum[u] of universes [0, count): the live cells and the checksum of
 // life_dev_checksum with the universe's own nx.
 hipError_t launch_batch_census(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, const uint32_t *cells,

@@ -64,15 +64,80 @@ struct BWArgs {
     RuleWords rule;
     const uint2 *rules;        // per-universe forms: (birth, survive) of universe u
     int64_t *period, *found;   // cycle detection: 0 / -1, or the period and the generation it was found at
+    uint32_t *trace;           // the recording forms: a.gens entries per universe, universe-major
 };
 
 // what a wave watches its universe for (LIFE_BATCH_OPT_SETTLE, LIFE_BATCH_OPT_CYCLE)
 enum Detector { kNoDetector = 0, kSettle = 1, kCycle = 2 };
 
+// The sum of x over the 64 lanes (every lane enabled), wave-uniform: four
+// row_shr adds leave a row's total in its lane 15, row_bcast:15 and
+// row_bcast:31 carry the totals up to lane 63.
+// (a lane the control or the row mask leaves without a source adds zero)
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint32_t dpp_from(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROWS, 0xf, true);
+}
+// the totals of the four 16-lane rows, each in its lane 15
+__device__ __forceinline__ uint32_t row_totals(uint32_t x) {
+    x += dpp_from<0x111, 0xf>(x);  // row_shr:1
+    x += dpp_from<0x112, 0xf>(x);  // row_shr:2
+    x += dpp_from<0x114, 0xf>(x);  // row_shr:4
+    x += dpp_from<0x118, 0xf>(x);  // row_shr:8
+    return x;
+}
+__device__ __forceinline__ uint32_t wave_total(uint32_t x) {
+    x = row_totals(x);
+    x += dpp_from<0x142, 0xa>(x);  // row_bcast:15 into rows 1 and 3
+    x += dpp_from<0x143, 0xc>(x);  // row_bcast:31 into rows 2 and 3
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+
+// The population trace of a wave (LIFE_BATCH_OPT_POPULATION):
+// the live cells of its universe after every generation, kept in registers and
+// flushed every kTraceFlush generations.  A wave-tier total is at most 128 x
+// 64 = 8192, so two generations ride the halves of one dword through one
+// wave_total: the lanes' counts of an even pending generation wait in `half`,
+// the odd one joins them above bit 16, and lane k keeps the totals of pending
+// generations 2 k and 2 k + 1 in `pend`.
+constexpr int kTraceFlush = 128;
+
+struct WaveTrace {
+    uint32_t *at;  // the next entry to flush
+    uint32_t half = 0, pend = 0;
+    int k = 0;  // pending generations (wave-uniform)
+    int lane;
+    __device__ __forceinline__ WaveTrace(uint32_t *to, int lane_) : at(to), lane(lane_) {}
+    __device__ __forceinline__ void flush() {
+        if (2 * lane < k) at[2 * lane] = pend & 0xFFFFu;
+        if (2 * lane + 1 < k) at[2 * lane + 1] = pend >> 16;
+        at += k;
+        k = 0;
+    }
+    __device__ __forceinline__ void pair(uint32_t both) {
+        const uint32_t total = wave_total(both);
+        if (lane == k >> 1) pend = total;
+    }
+    // after a generation: `count` the live cells of this lane's row
+    __device__ __forceinline__ void record(uint32_t count) {
+        if (k & 1)
+            pair(half | count << 16);
+        else
+            half = count;
+        if (++k == kTraceFlush) flush();
+    }
+    __device__ __forceinline__ void finish() {
+        if (k & 1) pair(half);
+        flush();
+    }
+};
+
 // The whole life of a wave that owns universe u: load, a.gens generations under
 // rp (fewer when the detector lets it leave early), store.  Shared by every
-// wave-tier kernel.
-template <int W, int DET, class RP>
+// wave-tier kernel.  POP: the recording forms.  Every generation of the call is
+// computed and its live count recorded, whatever the detector finds or found
+// in an earlier call: it flags what it flags without POP and the wave runs on.
+template <int W, int DET, bool POP = false, class RP>
 __device__ __forceinline__ void wave_body(const BWArgs &a, const int64_t u, const int lane, const RP &rp) {
     constexpr bool SETTLE = DET == kSettle, CYCLE = DET == kCycle;
     const int ny = a.ny;
@@ -91,7 +156,7 @@ __device__ __forceinline__ void wave_body(const BWArgs &a, const int64_t u, cons
     bool detect = false;
     if (SETTLE) {
         detect = a.settled[u] < 0;
-        if (!detect) gens &= 1;  // settled in an earlier call: the state has period 1 or 2
+        if (!detect && !POP) gens &= 1;  // settled in an earlier call: the state has period 1 or 2
     }
     uint32_t p1[SETTLE ? W : 1], p2[SETTLE ? W : 1];  // S_(g-1), S_(g-2)
     if (SETTLE) {
@@ -106,10 +171,11 @@ __device__ __forceinline__ void wave_body(const BWArgs &a, const int64_t u, cons
         // (the same for every lane: tell the compiler so, and the loops below branch on scalars)
         const uint32_t known = __builtin_amdgcn_readfirstlane((uint32_t)a.period[u]);
         detect = known == 0u;
-        if (!detect) gens = (int)((uint32_t)gens % known);  // found in an earlier call
+        if (!detect && !POP) gens = (int)((uint32_t)gens % known);  // found in an earlier call
 #pragma unroll
         for (int j = 0; j < W; ++j) T[j] = v[j];
     }
+    WaveTrace tr(POP ? a.trace + (size_t)u * (size_t)a.gens : nullptr, lane);
     auto generation = [&]() {
         uint32_t s0[W], s1[W];
 #pragma unroll
@@ -127,6 +193,12 @@ __device__ __forceinline__ void wave_body(const BWArgs &a, const int64_t u, cons
             v[j] = rp(a0, a1, s0[j], s1[j], d0, d1, v[j]);
         }
         v[W - 1] &= xw.keep;
+        if (POP) {
+            uint32_t c = 0;
+#pragma unroll
+            for (int j = 0; j < W; ++j) c += __popc(v[j]);
+            tr.record(c);
+        }
     };
     if (CYCLE) {
         // The detecting generations, then the rest without: what is recorded is
@@ -153,7 +225,7 @@ __device__ __forceinline__ void wave_body(const BWArgs &a, const int64_t u, cons
                     a.period[u] = (int64_t)lam;
                     a.found[u] = a.gen0 + g;
                 }
-                rest = (int)((uint32_t)(gens - g) % lam);
+                rest = POP ? gens - g : (int)((uint32_t)(gens - g) % lam);
             }
         }
         for (g = 0; g < rest; ++g) generation();
@@ -168,7 +240,7 @@ __device__ __forceinline__ void wave_body(const BWArgs &a, const int64_t u, cons
                 if (__builtin_amdgcn_ballot_w64(diff != 0u) == 0ull) {  // S_g == S_(g-2), the whole wave agrees
                     if (lane == 0) a.settled[u] = a.gen0 + g;
                     detect = false;
-                    gens = g + ((gens - g) & 1);
+                    if (!POP) gens = g + ((gens - g) & 1);
                 }
             }
 #pragma unroll
@@ -178,6 +250,7 @@ __device__ __forceinline__ void wave_body(const BWArgs &a, const int64_t u, cons
             }
         }
     }
+    if (POP) tr.finish();
     if (!active) return;
 #pragma unroll
     for (int j = 0; j < W; ++j) row[j] = v[j];
@@ -256,6 +329,32 @@ hipError_t launch_survey(const BWArgs &a, int rule, int det, unsigned blocks, hi
     return hipGetLastError();
 }
 
+// The recording forms: every two-state form of the wave tier,
+// the uniform ones included, with the population trace of wave_body on.
+template <int W, int RULE, int DET>
+__global__ __launch_bounds__(64 * kBatchWaves) void batch_trace_kernel(BWArgs a) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t u = (int64_t)blockIdx.x * kBatchWaves + (int64_t)(threadIdx.x >> 6);
+    if (u >= a.count) return;  // the whole wave
+    if (RULE == kSurveyConway)
+        wave_body<W, DET, true>(a, u, lane, ConwayRule{});
+    else if (RULE == kSurveyTable)
+        wave_body<W, DET, true>(a, u, lane, TableRule(a.rule));
+    else
+        wave_body<W, DET, true>(a, u, lane, universe_rule(a.rules, u));
+}
+
+template <int W, int RULE>
+hipError_t launch_trace(const BWArgs &a, int det, unsigned blocks, hipStream_t s) {
+    if (det == kCycle)
+        batch_trace_kernel<W, RULE, kCycle><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
+    else if (det == kSettle)
+        batch_trace_kernel<W, RULE, kSettle><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
+    else
+        batch_trace_kernel<W, RULE, kNoDetector><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
+    return hipGetLastError();
+}
+
 // ----------------------------------------------------------------- group tier
 // One universe per workgroup: the technique of the small-grid register kernel
 // (life_kernels.hip rsmall_kernel without its window) on the batch storage.
@@ -267,14 +366,24 @@ hipError_t launch_survey(const BWArgs &a, int rule, int det, unsigned blocks, hi
 // strip above's last and the strip below's first (periodic in y), and applies
 // B3/S23 to its rows.  The exchange is double-buffered by the generation's
 // parity: a slot is rewritten two generations later, behind the next barrier.
+//
+// POP, the recording form: after a generation every thread
+// counts its R rows and each wave leaves its total in `part`, double-buffered
+// by the same parity.  Behind the barrier of the next generation (the one
+// after the loop for the last) wave 0 adds the waves' totals up and one lane
+// stores the entry: the loop keeps its one barrier.  Totals reach 2048 x 512.
 struct BGArgs {
     uint32_t *cells;
     int32_t nx, ny, W, lgWp, gens, ns;
+    uint32_t *trace;  // the recording form: a.gens entries per universe, universe-major
 };
 
-template <int R>
-__global__ __launch_bounds__(kBatchGroupThreads) void batch_group_kernel(BGArgs a) {
+constexpr int kBatchGroupWaves = kBatchGroupThreads / 64;
+
+template <int R, bool POP>
+__device__ __forceinline__ void group_body(const BGArgs &a) {
     __shared__ uint32_t xch[2][4][kBatchGroupThreads];  // [parity][top s0/s1, bottom s0/s1][thread]
+    __shared__ uint32_t part[POP ? 2 : 1][POP ? kBatchGroupWaves : 1];  // [parity][wave]: live cells of a generation
     const int t = (int)threadIdx.x;
     const int Wp = 1 << a.lgWp, W = a.W;
     const int j = t & (Wp - 1);  // word column
@@ -301,6 +410,14 @@ __global__ __launch_bounds__(kBatchGroupThreads) void batch_group_kernel(BGArgs 
         c = b3<kKeepMux>(c, keep, rw << xw.qs);  // the last word gets cell 0 at bit q
         BitEnc::fa(__builtin_amdgcn_alignbit(c, l, 31), c, __builtin_amdgcn_alignbit(rw, c, 1), s0, s1);
     };
+    // wave 0 behind a barrier: entry g of the trace from the waves' totals in part[g & 1]
+    uint32_t *const entries = POP ? a.trace + (size_t)blockIdx.x * (size_t)a.gens : nullptr;
+    const int waves = (int)(blockDim.x >> 6);
+    auto publish = [&](int g) {
+        if (t >= 64) return;
+        const uint32_t sum = row_totals(t < waves ? part[g & 1][t & (kBatchGroupWaves - 1)] : 0u);
+        if (t == kBatchGroupWaves - 1) entries[g] = sum;
+    };
     for (int g = 0; g < a.gens; ++g) {
         const int par = g & 1;
         uint32_t h0[R], h1[R];
@@ -311,6 +428,7 @@ __global__ __launch_bounds__(kBatchGroupThreads) void batch_group_kernel(BGArgs 
         xch[par][2][t] = h0[R - 1];
         xch[par][3][t] = h1[R - 1];
         __syncthreads();
+        if (POP && g > 0) publish(g - 1);
         const uint32_t a0 = xch[par][2][ta], a1 = xch[par][3][ta];
         const uint32_t d0 = xch[par][0][tb], d1 = xch[par][1][tb];
 #pragma unroll
@@ -324,10 +442,32 @@ __global__ __launch_bounds__(kBatchGroupThreads) void batch_group_kernel(BGArgs 
             v[0] = BitEnc::rule1(a0, a1, h0[0], h1[0], h0[1], h1[1], v[0]) & keep;
             v[R - 1] = BitEnc::rule1(h0[R - 2], h1[R - 2], h0[R - 1], h1[R - 1], d0, d1, v[R - 1]) & keep;
         }
+        if (POP) {
+            uint32_t c = 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) c += __popc(v[r]);
+            c = wave_total(active ? c : 0u);  // (a thread without a strip computes on what it reads, and is never stored)
+            if ((t & 63) == 0) part[par][t >> 6] = c;
+        }
+    }
+    if (POP) {
+        __syncthreads();
+        publish(a.gens - 1);
     }
     if (!active) return;
 #pragma unroll
     for (int r = 0; r < R; ++r) uni[(size_t)(y0 + r) * W + j] = v[r];
+}
+
+template <int R>
+__global__ __launch_bounds__(kBatchGroupThreads) void batch_group_kernel(BGArgs a) {
+    group_body<R, false>(a);
+}
+
+// (a name of its own: the instances above are counted by theirs)
+template <int R>
+__global__ __launch_bounds__(kBatchGroupThreads) void batch_trace_group_kernel(BGArgs a) {
+    group_body<R, true>(a);
 }
 
 // ------------------------------------------------------------- data movement
@@ -761,8 +901,44 @@ hipError_t launch_batch_survey(const BatchPlan &p, int64_t nx, int64_t ny, int64
     }
 }
 
-hipError_t launch_batch_group(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
-                              int64_t gens, hipStream_t s) {
+hipError_t launch_batch_trace(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
+                              const RuleWords *rule, const uint32_t *rules, bool settle, int64_t *settled, bool cycle,
+                              int64_t *period, int64_t *found, int64_t gen0, uint32_t *trace, hipStream_t s) {
+    if (p.tier != LIFE_BATCH_TIER_WAVE || gens < 1 || gens > INT32_MAX || (settle && !settled) || (settle && cycle) ||
+        (cycle && (!period || !found)) || !trace || count * gens > kBatchTraceEntries ||
+        !grid_ok((count + kBatchWaves - 1) / kBatchWaves))
+        return hipErrorInvalidValue;
+    BWArgs a{};
+    a.cells = cells;
+    a.settled = settled;
+    a.count = count;
+    a.gen0 = gen0;
+    a.nx = (int32_t)nx;
+    a.ny = (int32_t)ny;
+    a.gens = (int32_t)gens;
+    if (rule) a.rule = *rule;
+    a.rules = reinterpret_cast<const uint2 *>(rules);
+    a.period = period;
+    a.found = found;
+    a.trace = trace;
+    const int r = rules ? kSurveyPerUniverse : rule ? kSurveyTable : kSurveyConway;
+    const int det = cycle ? kCycle : settle ? kSettle : kNoDetector;
+    const unsigned blocks = wave_blocks(count);
+    switch (p.words * 4 + r) {
+#define LIFE_BT(N) \
+    case N * 4 + kSurveyConway: return launch_trace<N, kSurveyConway>(a, det, blocks, s); \
+    case N * 4 + kSurveyTable: return launch_trace<N, kSurveyTable>(a, det, blocks, s); \
+    case N * 4 + kSurveyPerUniverse: return launch_trace<N, kSurveyPerUniverse>(a, det, blocks, s);
+        LIFE_BT(1) LIFE_BT(2) LIFE_BT(3) LIFE_BT(4)
+#undef LIFE_BT
+    default: return hipErrorInvalidValue;
+    }
+}
+
+namespace {
+
+hipError_t launch_group(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
+                        uint32_t *trace, hipStream_t s) {
     if (p.tier != LIFE_BATCH_TIER_GROUP || gens < 1 || gens > INT32_MAX || !grid_ok(count)) return hipErrorInvalidValue;
     BGArgs a{};
     a.cells = cells;
@@ -772,18 +948,37 @@ hipError_t launch_batch_group(const BatchPlan &p, int64_t nx, int64_t ny, int64_
     a.lgWp = p.lg_wp;
     a.gens = (int32_t)gens;
     a.ns = p.strips;
+    a.trace = trace;
     // only the waves that own strips (the barrier counts the launched waves)
     const unsigned threads = 64u * (unsigned)p.waves_per_group;
     if (threads > (unsigned)kBatchGroupThreads) return hipErrorInvalidValue;
     switch (p.rows) {
 #define LIFE_BG(N) \
-    case N: batch_group_kernel<N><<<(unsigned)count, threads, 0, s>>>(a); break;
+    case N: \
+        if (trace) \
+            batch_trace_group_kernel<N><<<(unsigned)count, threads, 0, s>>>(a); \
+        else \
+            batch_group_kernel<N><<<(unsigned)count, threads, 0, s>>>(a); \
+        break;
         LIFE_BG(1) LIFE_BG(2) LIFE_BG(3) LIFE_BG(4) LIFE_BG(5) LIFE_BG(6) LIFE_BG(8) LIFE_BG(10) LIFE_BG(12)
         LIFE_BG(16) LIFE_BG(20) LIFE_BG(25) LIFE_BG(32)
 #undef LIFE_BG
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_batch_group(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
+                              int64_t gens, hipStream_t s) {
+    return launch_group(p, nx, ny, count, cells, gens, nullptr, s);
+}
+
+hipError_t launch_batch_group_trace(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
+                                    int64_t gens, uint32_t *trace, hipStream_t s) {
+    if (!trace || count * gens > kBatchTraceEntries) return hipErrorInvalidValue;
+    return launch_group(p, nx, ny, count, cells, gens, trace, s);
 }
 
 hipError_t launch_batch_census(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, const uint32_t *cells,

@@ -27,9 +27,20 @@ states (four) and, in the same run, uniform HighLife on the two-state table
 kernel as the yardstick; then one line with a (rule, C) per universe, the four
 rules in turn.
 
+The population lines, reported and not gated: 64 x 64 and
+128 x 64 at 16384 and 262144 universes and 500 x 500 at 4096, 50 % soups,
+step(1024), each measured three ways in one process, alternating within every
+repetition: (a) LIFE_BATCH_OPT_POPULATION off, (b) on, (c) the host loop the
+option replaces, step(1) + live_counts() per generation on the batch of (a),
+over --loop-gens generations and scaled to 1024 by 1024 / loop-gens (every
+generation of the loop costs the same launches and readbacks).  Before any
+timing the trace of (b) over loop-gens generations is compared with the counts
+of (c).  read_s is life_batch_population of the whole trace, after the call.
+
     python scripts/batch_bench.py --out profiles/batch/batch_bench.jsonl
     python scripts/batch_bench.py --only survey --out profiles/batch/survey_bench.jsonl
     python scripts/batch_bench.py --only gen --out profiles/batch/gen_bench.jsonl
+    python scripts/batch_bench.py --only population --out profiles/batch/population_bench.jsonl
 """
 import argparse
 import json
@@ -41,10 +52,13 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mpi-and-open-mp_amd"))
 
+import numpy as np  # noqa: E402
+
 import life_mi355x as lm  # noqa: E402
 
 ROWS = [((32, 32), (1024, 16384, 262144)), ((64, 64), (1024, 16384, 262144)), ((128, 64), (1024, 16384, 262144)),
         ((500, 500), (256, 4096))]
+POPULATION_ROWS = [((64, 64), (16384, 262144)), ((128, 64), (16384, 262144)), ((500, 500), (4096,))]
 SEED = 1234
 
 
@@ -105,6 +119,48 @@ def baseline_time(nx, ny, count, gens, reps, density=0.5):
     return statistics.median(t), min(t), max(t), sorted(paths), sums
 
 
+def spread(times):
+    return {"s": statistics.median(times), "min_s": min(times), "max_s": max(times)}
+
+
+def population_row(nx, ny, count, gens, loop_gens, reps):
+    """One population line: (a) option off, (b) option on, (c) the host loop, alternating."""
+    with lm.LifeBatch(nx, ny, count) as off, lm.LifeBatch(nx, ny, count, population=True) as on:
+        def loop():
+            return np.stack([(off.step(1), off.live_counts())[1] for _ in range(loop_gens)], axis=1)
+
+        # the traces of (b) and (c) first
+        for b in (off, on):
+            b.fill_random(SEED, 0.5)
+        on.step(loop_gens)
+        if not np.array_equal(on.population(), loop()):
+            raise SystemExit(f"{nx}x{ny} x {count}: the trace and the host loop disagree")
+        a_t, b_t, c_t, read_t = [], [], [], []
+        for rep in range(reps + 1):  # the first is the warm-up
+            off.fill_random(SEED, 0.5)
+            a_t.append(timed(lambda: off.step(gens), off.sync))
+            on.fill_random(SEED, 0.5)
+            b_t.append(timed(lambda: on.step(gens), on.sync))
+            read_t.append(timed(on.population, on.sync))
+            off.fill_random(SEED, 0.5)
+            c_t.append(timed(loop, off.sync))
+        # the host loop ran last on the plain batch: the recording one to the same generation
+        on.fill_random(SEED, 0.5)
+        on.step(loop_gens)
+        if list(off.checksums()) != list(on.checksums()):
+            raise SystemExit(f"{nx}x{ny} x {count}: option on and off disagree")
+    scale = gens / loop_gens
+    a, b, c, read = (spread(t[1:]) for t in (a_t, b_t, c_t, read_t))
+    row = {"population": True, "shape": [nx, ny], "count": count, "gens": gens, "tier": lm.batch_query(nx, ny)[0],
+           "loop_gens": loop_gens, "loop_scale": scale}
+    for name, t in (("off", a), ("on", b), ("read", read), ("loop", c)):
+        row.update({f"{name}_{k}": v for k, v in t.items()})
+    row.update({"loop_scaled_s": c["s"] * scale, "on_over_off": b["s"] / a["s"],
+                "loop_over_on": c["s"] * scale / b["s"], "loop_over_on_and_read": c["s"] * scale / (b["s"] + read["s"]),
+                "off_tcups": nx * ny * count * gens / a["s"] / 1e12, "on_tcups": nx * ny * count * gens / b["s"] / 1e12})
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--gens", type=int, default=1024)
@@ -113,8 +169,10 @@ def main():
     ap.add_argument("--settle-gens", type=int, default=4096)
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="the smallest count of every shape only")
-    ap.add_argument("--only", choices=("all", "table", "settle", "survey", "gen"), default="all",
-                    help="the shape table, the settle line, the survey lines or the Generations lines alone")
+    ap.add_argument("--loop-gens", type=int, default=32, help="generations of the population lines' host loop")
+    ap.add_argument("--only", choices=("all", "table", "settle", "survey", "gen", "population"), default="all",
+                    help="the shape table, the settle line, the survey lines, the Generations lines or the "
+                         "population lines alone")
     a = ap.parse_args()
     out = open(a.out, "w") if a.out else None
 
@@ -194,6 +252,10 @@ def main():
         emit({"generations": True, "shape": [nx, ny], "count": count, "gens": a.gens, "rule": "per universe",
               "rules": mix, "planes": 4, "s": t[0], "min_s": t[1], "max_s": t[2], "tcups": updates / t[0] / 1e12,
               "over_highlife": t[0] / yard[0]})
+    for (nx, ny), counts in POPULATION_ROWS if a.only in ("all", "population") else []:
+        for count in counts[:1] if a.quick else counts:
+            emit(population_row(nx, ny, min(count, 1024) if a.quick else count, a.gens, min(a.loop_gens, a.gens),
+                                a.reps))
     print("| shape | count | batch ms | host loop ms (scaled) | ratio | Tcell-updates/s |", file=sys.stderr)
     print("|---|---|---|---|---|---|", file=sys.stderr)
     for r in table:
