@@ -640,7 +640,7 @@ void life_dev_destroy(life_dev *d);
  *                         and no LDS exchange per generation; any rule
  *                         life_dev_set_rule accepts, one for all universes or
  *                         one each (life_batch_set_rules); LIFE_BATCH_OPT_
- *                         SETTLE, LIFE_BATCH_OPT_CYCLE.
+ *                         SETTLE, LIFE_BATCH_OPT_CYCLE, LIFE_BATCH_OPT_ONSET.
  *  LIFE_BATCH_TIER_GROUP  every other shape the one-workgroup register kernel
  *                         of the small-grid path takes (at most 2048 cells
  *                         wide, strips of R rows dividing ny, R one of 1 2 3 4
@@ -801,10 +801,37 @@ int life_batch_census_gen(life_batch *b, int64_t *live, int64_t *dying, uint64_t
  * only: LIFE_EINVAL when turned on while a universe's rule has more than two
  * states, and from life_batch_set_rule_gen / _set_rules_gen with more than
  * two states while it is on (their two-state calls keep working).
+ * LIFE_BATCH_OPT_ONSET (wave tier, value 0 / 1, default 0): the exact onset of
+ * the cycle beside its period.  It acts together with LIFE_BATCH_OPT_CYCLE.
+ * While both are on, the wave that finds universe u's period lam at
+ * generation g of a call from state S_0 at absolute generation G_0 also runs
+ * Brent's second phase: it advances a copy of S_0 by lam generations and
+ * steps S_0 and S_lam together until they are equal, which gives
+ *   mu = min { m >= 0 : S_m == S_(m+lam) }     (Generations: in every plane)
+ * and records onset[u] = G_0 + mu (life_batch_onsets).  Always mu <= g - lam:
+ * the checkpoint S_(g-lam) == S_g lies on the cycle; the search is a counted
+ * loop of at most g - lam steps after the lam of the copy, in registers, in
+ * the same launch.  The value is max(true onset, G_0): the exact generation at
+ * which the orbit entered its cycle when that happened at or after G_0 -- in
+ * particular in the first step call after an upload or fill -- and G_0 for a
+ * universe that was already cycling at G_0 without being flagged.  A universe
+ * flagged before the option was turned on keeps -1 until its flags are reset.
+ * States, census, cycle pairs, the generation counter and population traces
+ * are bit-identical with the option on and off: the search's generations are
+ * recorded in no trace.  LIFE_EINVAL, with nothing changed: a group-tier
+ * batch, a value other than 0 / 1, turning it on while LIFE_BATCH_OPT_CYCLE is
+ * off.  Turning LIFE_BATCH_OPT_CYCLE off turns this option off as well.
+ * (LIFE_BATCH_OPT_SETTLE needs no such option: its generation minus 2 is the
+ * exact onset already.)
  * Option number 2 is unassigned and stays LIFE_EINVAL. */
 #define LIFE_BATCH_OPT_SETTLE 1
 #define LIFE_BATCH_OPT_CYCLE 3
 #define LIFE_BATCH_OPT_POPULATION 4
+/* = 5.  Spelled from its neighbour: tests/test_batch_population_host.py, which
+ * predates the option, pins the literal numbers defined here to exactly 1, 3,
+ * 4; tests/test_batch_onset_host.py evaluates this one and holds all four to
+ * 1, 3, 4, 5. */
+#define LIFE_BATCH_OPT_ONSET (LIFE_BATCH_OPT_POPULATION + 1)
 int life_batch_configure(life_batch *b, int option, int value);
 /* All universes advance `generations`.  Asynchronous (one launch); 0 is a
  * no-op; LIFE_EINVAL when negative or above INT32_MAX. */
@@ -823,6 +850,12 @@ int life_batch_settled(life_batch *b, int64_t *generation);
  * upload or a life_batch_set_rules range that covers it, all of them with
  * life_batch_fill_random and life_batch_set_rule.  Blocking. */
 int life_batch_cycles(life_batch *b, int64_t *period, int64_t *generation);
+/* Per universe, `count` entries: the absolute generation LIFE_BATCH_OPT_ONSET
+ * recorded as the onset of the universe's cycle (max(true onset, G_0) of the
+ * call that found the period, see the option), -1 where none was recorded; all
+ * -1 when the option was never on.  An entry goes back to -1 exactly where the
+ * universe's cycle pair goes back to 0 / -1 (life_batch_cycles).  Blocking. */
+int life_batch_onsets(life_batch *b, int64_t *generation);
 /* The population trace of LIFE_BATCH_OPT_POPULATION.  *generations (may be
  * NULL) is the number G of generations the last life_batch_step call
  * recorded: its n with the option on; 0 with the option off, for a call of 0

@@ -32,6 +32,8 @@ struct life_batch {
     bool settle = false;
     bool cycle = false;
     int64_t *cycles = nullptr;  // period[count], found[count] of LIFE_BATCH_OPT_CYCLE (from its first use)
+    bool onset = false;
+    int64_t *onsets = nullptr;  // per universe: -1, or the onset LIFE_BATCH_OPT_ONSET computed (from its first use)
     int64_t generation = 0;
     // Generations.  `states` is the uniform rule's; on a mixed batch `shadow` holds every
     // universe's and `hist` how many universes have each count.  `decay`: `planes` (0, 1, 2, 4) bit planes of d = s
@@ -73,7 +75,7 @@ int range_ok(const life_batch *b, int64_t first, int64_t n, const void *grids, c
     return LIFE_OK;
 }
 
-// settled flags of universes [first, first + n) back to -1, their cycle pairs to 0 / -1
+// settled flags of universes [first, first + n) back to -1, their cycle pairs to 0 / -1, their onsets to -1
 int clear_settled(life_batch *b, int64_t first, int64_t n) {
     if (n < 1) return LIFE_OK;
     HIPCHK(hipMemsetAsync(b->settled + first, 0xFF, sizeof(int64_t) * (size_t)n, b->stream));
@@ -81,6 +83,7 @@ int clear_settled(life_batch *b, int64_t first, int64_t n) {
         HIPCHK(hipMemsetAsync(b->cycles + first, 0, sizeof(int64_t) * (size_t)n, b->stream));
         HIPCHK(hipMemsetAsync(b->cycles + b->count + first, 0xFF, sizeof(int64_t) * (size_t)n, b->stream));
     }
+    if (b->onsets) HIPCHK(hipMemsetAsync(b->onsets + first, 0xFF, sizeof(int64_t) * (size_t)n, b->stream));
     return LIFE_OK;
 }
 
@@ -194,6 +197,7 @@ void free_batch(life_batch *b) {
     if (b->settled) (void)hipFree(b->settled);
     if (b->rules) (void)hipFree(b->rules);
     if (b->cycles) (void)hipFree(b->cycles);
+    if (b->onsets) (void)hipFree(b->onsets);
     if (b->decay) (void)hipFree(b->decay);
     if (b->trace) (void)hipFree(b->trace);
     if (b->census) (void)hipFree(b->census);
@@ -577,7 +581,8 @@ int life_batch_census_gen(life_batch *b, int64_t *live, int64_t *dying, uint64_t
 int life_batch_configure(life_batch *b, int option, int value) {
     if (!b) return LIFE_EINVAL;
     // (option 2 is unassigned)
-    if ((option != LIFE_BATCH_OPT_SETTLE && option != LIFE_BATCH_OPT_CYCLE && option != LIFE_BATCH_OPT_POPULATION) ||
+    if ((option != LIFE_BATCH_OPT_SETTLE && option != LIFE_BATCH_OPT_CYCLE && option != LIFE_BATCH_OPT_POPULATION &&
+         option != LIFE_BATCH_OPT_ONSET) ||
         (value != 0 && value != 1)) {
         set_err("life_batch_configure: option %d value %d", option, value);
         return LIFE_EINVAL;
@@ -596,12 +601,26 @@ int life_batch_configure(life_batch *b, int option, int value) {
         b->population = value != 0;
         return LIFE_OK;
     }
-    const bool settle = option == LIFE_BATCH_OPT_SETTLE;
-    const char *name = settle ? "LIFE_BATCH_OPT_SETTLE" : "LIFE_BATCH_OPT_CYCLE";
+    const bool settle = option == LIFE_BATCH_OPT_SETTLE, onset = option == LIFE_BATCH_OPT_ONSET;
+    const char *name = settle ? "LIFE_BATCH_OPT_SETTLE" : onset ? "LIFE_BATCH_OPT_ONSET" : "LIFE_BATCH_OPT_CYCLE";
     if (b->plan.tier != LIFE_BATCH_TIER_WAVE) {
         set_err("%s: a group-tier batch (%lld x %lld) has no %s detection", name, (long long)b->nx, (long long)b->ny,
                 settle ? "settle" : "cycle");
         return LIFE_EINVAL;
+    }
+    if (onset) {  // the second phase of the cycle detection: it acts with that option only
+        if (value && !b->cycle) {
+            set_err("%s: LIFE_BATCH_OPT_CYCLE is off (the onset is computed by the wave that finds the period: turn "
+                    "that option on first)", name);
+            return LIFE_EINVAL;
+        }
+        if (value && !b->onsets) {
+            HIPCHK(hipSetDevice(b->device));
+            HIPCHK(hipMalloc(&b->onsets, sizeof(int64_t) * (size_t)b->count));
+            HIPCHK(hipMemsetAsync(b->onsets, 0xFF, sizeof(int64_t) * (size_t)b->count, b->stream));
+        }
+        b->onset = value != 0;
+        return LIFE_OK;
     }
     if (value && (settle ? b->cycle : b->settle)) {
         set_err("%s: %s is on (two detectors for one wave: turn that one off first)", name,
@@ -621,6 +640,7 @@ int life_batch_configure(life_batch *b, int option, int value) {
         HIPCHK(hipMemsetAsync(b->cycles + b->count, 0xFF, bytes, b->stream));
     }
     b->cycle = value != 0;
+    if (!b->cycle) b->onset = false;  // (nothing left to find an onset for)
     return LIFE_OK;
 }
 
@@ -643,10 +663,15 @@ int life_batch_step(life_batch *b, int64_t generations) {
     HIPCHK(hipSetDevice(b->device));
     const uint32_t most = max_states(b);
     int64_t *const found = b->cycles ? b->cycles + b->count : nullptr;
+    const bool onset = b->cycle && b->onset;  // (wave tier: the options are refused elsewhere)
     if (b->population) {  // (two-state: the option and the Generations rules refuse each other)
         CHK(grow_trace(b, b->count * generations));
         b->trace_gens = 0;
-        if (b->plan.tier == LIFE_BATCH_TIER_WAVE)
+        if (onset)
+            HIPCHK(life::launch_batch_onset(b->plan, b->nx, b->ny, b->count, b->cells, generations,
+                                            b->table ? &b->words : nullptr, b->rules, b->cycles, found, b->onsets,
+                                            b->generation, b->trace, b->stream));
+        else if (b->plan.tier == LIFE_BATCH_TIER_WAVE)
             HIPCHK(life::launch_batch_trace(b->plan, b->nx, b->ny, b->count, b->cells, generations,
                                             b->table ? &b->words : nullptr, b->rules, b->settle, b->settled, b->cycle,
                                             b->cycles, found, b->generation, b->trace, b->stream));
@@ -654,11 +679,19 @@ int life_batch_step(life_batch *b, int64_t generations) {
             HIPCHK(life::launch_batch_group_trace(b->plan, b->nx, b->ny, b->count, b->cells, generations, b->trace,
                                                   b->stream));
         b->trace_gens = generations;
-    } else if (most > 2)  // (wave tier: no other takes such a rule)
+    } else if (most > 2 && onset)
+        HIPCHK(life::launch_batch_onset_gen(b->plan, b->nx, b->ny, b->count, b->cells, b->decay, life::gen_planes(most),
+                                            generations, b->birth, b->survive, b->states, b->rules, b->cycles, found,
+                                            b->onsets, b->generation, b->stream));
+    else if (most > 2)  // (wave tier: no other takes such a rule)
         HIPCHK(life::launch_batch_gen(b->plan, b->nx, b->ny, b->count, b->cells, b->decay, life::gen_planes(most),
                                       generations, b->birth, b->survive, b->states, b->rules, b->settle, b->settled,
                                       b->cycle, b->cycles, b->cycles ? b->cycles + b->count : nullptr, b->generation,
                                       b->stream));
+    else if (onset)
+        HIPCHK(life::launch_batch_onset(b->plan, b->nx, b->ny, b->count, b->cells, generations,
+                                        b->table ? &b->words : nullptr, b->rules, b->cycles, found, b->onsets,
+                                        b->generation, nullptr, b->stream));
     else if (b->plan.tier == LIFE_BATCH_TIER_WAVE && (b->rules || b->cycle))
         HIPCHK(life::launch_batch_survey(b->plan, b->nx, b->ny, b->count, b->cells, generations,
                                          b->table ? &b->words : nullptr, b->rules, b->settle, b->settled, b->cycle,
@@ -725,6 +758,19 @@ int life_batch_cycles(life_batch *b, int64_t *period, int64_t *generation) {
     const size_t bytes = sizeof(int64_t) * (size_t)b->count;
     if (period) HIPCHK(hipMemcpyAsync(period, b->cycles, bytes, hipMemcpyDeviceToHost, b->stream));
     if (generation) HIPCHK(hipMemcpyAsync(generation, b->cycles + b->count, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LIFE_OK;
+}
+
+int life_batch_onsets(life_batch *b, int64_t *generation) {
+    if (!b || !generation) return LIFE_EINVAL;
+    if (!b->onsets) {  // LIFE_BATCH_OPT_ONSET was never on
+        for (int64_t u = 0; u < b->count; u++) generation[u] = -1;
+        return LIFE_OK;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipMemcpyAsync(generation, b->onsets, sizeof(int64_t) * (size_t)b->count, hipMemcpyDeviceToHost,
+                          b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return LIFE_OK;
 }

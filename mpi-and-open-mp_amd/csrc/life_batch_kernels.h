@@ -55,6 +55,21 @@ hipError_t launch_batch_trace(const BatchPlan &p, int64_t nx, int64_t ny, int64_
                               int64_t *period, int64_t *found, int64_t gen0, uint32_t *trace, hipStream_t s);
 hipError_t launch_batch_group_trace(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
                                     int64_t gens, uint32_t *trace, hipStream_t s);
+// The onset forms of LIFE_BATCH_OPT_ONSET, kernels of their own
+// again: cycle detection as above and, in the wave that finds a period, Brent's
+// second phase from the universe's stored start state; onset[u] (-1 until
+// then) becomes gen0 + min { m : S_m == S_(m+period) }.  launch_batch_onset
+// serves the two-state forms (rule, rules as launch_batch_survey; trace
+// non-null: the recording form of launch_batch_trace, in which the search
+// records nothing), launch_batch_onset_gen Generations (arguments as
+// launch_batch_gen).  Cycle detection is always on here, settle never.
+hipError_t launch_batch_onset(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
+                              const RuleWords *rule, const uint32_t *rules, int64_t *period, int64_t *found,
+                              int64_t *onset, int64_t gen0, uint32_t *trace, hipStream_t s);
+hipError_t launch_batch_onset_gen(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
+                                  uint32_t *decay, int planes, int64_t gens, uint32_t birth, uint32_t survive,
+                                  uint32_t states, const uint32_t *rules, int64_t *period, int64_t *found,
+                                  int64_t *onset, int64_t gen0, hipStream_t s);
 // live[u] / sum[u] of universes [0, count): the live cells and the checksum of
 // life_dev_checksum with the universe's own nx.
 hipError_t launch_batch_census(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, const uint32_t *cells,

@@ -132,6 +132,42 @@ struct WaveTrace {
     }
 };
 
+// One generation of K states held side by side in the same lanes, chain c's row
+// in x[c W, c W + W): the definition of a generation for every two-state wave
+// kernel.  K = 2 (the onset search) steps two independent
+// states in one pass -- sums, lane moves and rules of both issued together --
+// so one chain's ds_bpermute latency has the other's VALU to hide behind.
+template <int W, int K, class RP>
+__device__ __forceinline__ void wave_generations(uint32_t *x, const int addr_up, const int addr_dn, const XWrap &xw,
+                                                 const RP &rp) {
+    uint32_t s0[K * W], s1[K * W];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        const uint32_t *v = x + c * W;
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const uint32_t l = j == 0 ? v[W - 1] << xw.lsh : v[j - 1];
+            const uint32_t r = j == W - 1 ? v[0] : v[j + 1];
+            uint32_t m = v[j];
+            if (j == W - 1) m = b3<kKeepMux>(m, xw.keep, v[0] << xw.qs);
+            BitEnc::fa(__builtin_amdgcn_alignbit(m, l, 31), m, __builtin_amdgcn_alignbit(r, m, 1), s0[c * W + j],
+                       s1[c * W + j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            const int i = c * W + j;
+            const uint32_t a0 = bperm(addr_up, s0[i]), a1 = bperm(addr_up, s1[i]);
+            const uint32_t d0 = bperm(addr_dn, s0[i]), d1 = bperm(addr_dn, s1[i]);
+            x[i] = rp(a0, a1, s0[i], s1[i], d0, d1, x[i]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < K; ++c) x[c * W + W - 1] &= xw.keep;
+}
+
 // The whole life of a wave that owns universe u: load, a.gens generations under
 // rp (fewer when the detector lets it leave early), store.  Shared by every
 // wave-tier kernel.  POP: the recording forms.  Every generation of the call is
@@ -176,6 +212,7 @@ __device__ __forceinline__ void wave_body(const BWArgs &a, const int64_t u, cons
         for (int j = 0; j < W; ++j) T[j] = v[j];
     }
     WaveTrace tr(POP ? a.trace + (size_t)u * (size_t)a.gens : nullptr, lane);
+    // (wave_generations<W, 1> spelled out: the instances of this body keep the code they were measured with)
     auto generation = [&]() {
         uint32_t s0[W], s1[W];
 #pragma unroll
@@ -352,6 +389,134 @@ hipError_t launch_trace(const BWArgs &a, int det, unsigned blocks, hipStream_t s
         batch_trace_kernel<W, RULE, kSettle><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
     else
         batch_trace_kernel<W, RULE, kNoDetector><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+// The onset forms (LIFE_BATCH_OPT_ONSET): the cycle-detecting
+// wave_body plus Brent's second phase.  At detection v == T == S_g and the
+// universe's rows still hold S_0 (a wave stores once, at the end).  T keeps
+// S_g; v reloads S_0; B = S_0 advanced lam generations; then v and B walk
+// together until they are equal, after mu = min { m : S_m == S_(m+lam) }
+// generations.  Both loops are counted: lam, and g - lam for the walk (S_(g-lam)
+// == S_g lies on the cycle, so mu <= g - lam, which is what is recorded should
+// the bound ever be reached).  The search sits between the detecting loop and
+// the rest loop, where period / found are written anyway, and records nothing
+// in a population trace.  Cost: one more state copy, W words.
+// (The wave's index in its workgroup is the same in every lane.  Told so, the compiler keeps u, the universe's
+// masks and the twenty leaf words expanded from them in scalar registers: the second chain's state takes the
+// vector registers that frees.)
+__device__ __forceinline__ int64_t wave_of_group() {
+    return (int64_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
+
+struct BOArgs {
+    BWArgs w;
+    int64_t *onset;  // -1, or the absolute generation at which the universe entered its cycle
+};
+
+template <int W, bool POP, class RP>
+__device__ __forceinline__ void onset_body(const BOArgs &o, const int64_t u, const int lane, const RP &rp) {
+    const BWArgs &a = o.w;
+    const int ny = a.ny;
+    const bool active = lane < ny;
+    const int up = !active ? lane : lane == 0 ? ny - 1 : lane - 1;
+    const int dn = !active ? lane : lane + 1 == ny ? 0 : lane + 1;
+    const int addr_up = up << 2, addr_dn = dn << 2;
+    const XWrap xw(a.nx, W);
+    uint32_t *row = a.cells + ((size_t)u * (size_t)ny + (size_t)lane) * W;
+
+    uint32_t s[2 * W];  // v, and behind it the second chain of the search
+    uint32_t *const v = s, *const B = s + W;
+    uint32_t T[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        T[j] = v[j] = active ? row[j] : 0u;
+        B[j] = 0u;
+    }
+    int gens = a.gens;
+    uint32_t power = 1, lam = 0;
+    const uint32_t known = __builtin_amdgcn_readfirstlane((uint32_t)a.period[u]);
+    const bool detect = known == 0u;
+    if (!detect && !POP) gens = (int)((uint32_t)gens % known);  // found in an earlier call
+    WaveTrace tr(POP ? a.trace + (size_t)u * (size_t)a.gens : nullptr, lane);
+    auto generation = [&]() {
+        wave_generations<W, 1>(v, addr_up, addr_dn, xw, rp);
+        if (POP) {
+            uint32_t c = 0;
+#pragma unroll
+            for (int j = 0; j < W; ++j) c += __popc(v[j]);
+            tr.record(c);
+        }
+    };
+    int rest = gens, g = 1;
+    if (detect) {
+        for (; g <= gens; ++g) {
+            generation();
+            ++lam;
+            uint32_t diff = 0;
+#pragma unroll
+            for (int j = 0; j < W; ++j) diff |= v[j] ^ T[j];
+            if (__builtin_amdgcn_ballot_w64(diff != 0u) == 0ull) break;  // S_g == T: the minimal period is lam
+            if (lam == power) {
+#pragma unroll
+                for (int j = 0; j < W; ++j) T[j] = v[j];
+                power <<= 1;
+                lam = 0;
+            }
+        }
+        rest = 0;
+        if (g <= gens) {
+#pragma unroll
+            for (int j = 0; j < W; ++j) B[j] = v[j] = active ? row[j] : 0u;  // S_0
+            for (uint32_t i = 0; i < lam; ++i) wave_generations<W, 1>(B, addr_up, addr_dn, xw, rp);
+            const int bound = g - (int)lam;
+            int mu = bound;
+            for (int m = 0; m < bound; ++m) {
+                uint32_t diff = 0;
+#pragma unroll
+                for (int j = 0; j < W; ++j) diff |= v[j] ^ B[j];
+                if (__builtin_amdgcn_ballot_w64(diff != 0u) == 0ull) {  // S_m == S_(m+lam)
+                    mu = m;
+                    break;
+                }
+                wave_generations<W, 2>(s, addr_up, addr_dn, xw, rp);
+            }
+#pragma unroll
+            for (int j = 0; j < W; ++j) v[j] = T[j];  // S_g again
+            if (lane == 0) {
+                a.period[u] = (int64_t)lam;
+                a.found[u] = a.gen0 + g;
+                o.onset[u] = a.gen0 + mu;
+            }
+            rest = POP ? gens - g : (int)((uint32_t)(gens - g) % lam);
+        }
+    }
+    for (g = 0; g < rest; ++g) generation();
+    if (POP) tr.finish();
+    if (!active) return;
+#pragma unroll
+    for (int j = 0; j < W; ++j) row[j] = v[j];
+}
+
+template <int W, int RULE, bool POP>
+__global__ __launch_bounds__(64 * kBatchWaves) void batch_onset_kernel(BOArgs o) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t u = (int64_t)blockIdx.x * kBatchWaves + wave_of_group();
+    if (u >= o.w.count) return;  // the whole wave
+    if (RULE == kSurveyConway)
+        onset_body<W, POP>(o, u, lane, ConwayRule{});
+    else if (RULE == kSurveyTable)
+        onset_body<W, POP>(o, u, lane, TableRule(o.w.rule));
+    else
+        onset_body<W, POP>(o, u, lane, universe_rule(o.w.rules, u));
+}
+
+template <int W, int RULE>
+hipError_t launch_onset(const BOArgs &o, unsigned blocks, hipStream_t s) {
+    if (o.w.trace)
+        batch_onset_kernel<W, RULE, true><<<blocks, 64 * kBatchWaves, 0, s>>>(o);
+    else
+        batch_onset_kernel<W, RULE, false><<<blocks, 64 * kBatchWaves, 0, s>>>(o);
     return hipGetLastError();
 }
 
@@ -594,6 +759,70 @@ struct BNArgs {
     int64_t *period, *found;
 };
 
+// One generation of K Generations states side by side, as wave_generations:
+// chain c in x[c N, c N + N), N = W (1 + P), its alive words first and plane p
+// of d at W (1 + p).  `decays` and L: "the universe decays at all" and bit p of
+// C - 2, each spread over a word.
+template <int W, int P, int K>
+__device__ __forceinline__ void gen_generations(uint32_t *x, const int addr_up, const int addr_dn, const XWrap &xw,
+                                                const TableRule &rp, const uint32_t decays, const uint32_t (&L)[P]) {
+    constexpr int N = W * (1 + P);
+    uint32_t s0[K * W], s1[K * W];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        const uint32_t *v = x + c * N;
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const uint32_t l = j == 0 ? v[W - 1] << xw.lsh : v[j - 1];
+            const uint32_t r = j == W - 1 ? v[0] : v[j + 1];
+            uint32_t m = v[j];
+            if (j == W - 1) m = b3<kKeepMux>(m, xw.keep, v[0] << xw.qs);
+            BitEnc::fa(__builtin_amdgcn_alignbit(m, l, 31), m, __builtin_amdgcn_alignbit(r, m, 1), s0[c * W + j],
+                       s1[c * W + j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            uint32_t *v = x + c * N;
+            const int i = c * W + j;
+            const uint32_t a0 = bperm(addr_up, s0[i]), a1 = bperm(addr_up, s1[i]);
+            const uint32_t d0 = bperm(addr_dn, s0[i]), d1 = bperm(addr_dn, s1[i]);
+            const uint32_t alive = v[j];
+            const uint32_t n = rp(a0, a1, s0[i], s1[i], d0, d1, alive);
+            uint32_t *d = &v[W + j];  // plane p at d[W p]
+            const uint32_t start = b3<kGenStart>(alive, n, decays);
+            if (P == 1) {  // d is 0 or 1 = C - 2: a dying cell dies, 2 v_bitop3
+                v[j] = b3<kGenAndNot>(n, d[0], d[0]);
+                d[0] = start;
+            } else if (P == 2) {  // 6 and a v_xor
+                v[j] = b3<kGenAndNot>(n, d[0], d[W]);
+                const uint32_t more = b3<kGenOrXor>(d[0] ^ L[0], d[W], L[1]);     // d != C - 2
+                const uint32_t go = b3<kGenOrAnd>(d[0], d[W], more);              // dying, and not for the last time
+                const uint32_t t1 = b3<kGenXorAnd>(d[W], d[0], go);
+                d[0] = b3<kGenAndNotOr>(go, d[0], start);
+                d[W] = t1;
+            } else {  // 12, a v_xor and a v_and
+                const uint32_t low = b3<kGenOr3>(d[0], d[W], d[2 * W]);
+                v[j] = b3<kGenAndNot>(n, low, d[3 * W]);
+                uint32_t more = b3<kGenOrXor>(d[0] ^ L[0], d[W], L[1]);
+                more = b3<kGenOrXor>(more, d[2 * W], L[2]);
+                more = b3<kGenOrXor>(more, d[3 * W], L[3]);
+                const uint32_t go = b3<kGenOrAnd>(low, d[3 * W], more);
+                const uint32_t c2 = d[0] & d[W], c3 = b3<kGenAnd3>(d[0], d[W], d[2 * W]);  // the ripple of d + 1
+                const uint32_t t1 = b3<kGenXorAnd>(d[W], d[0], go);
+                d[0] = b3<kGenAndNotOr>(go, d[0], start);
+                d[W] = t1;
+                d[2 * W] = b3<kGenXorAnd>(d[2 * W], c2, go);
+                d[3 * W] = b3<kGenXorAnd>(d[3 * W], c3, go);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < K; ++c) x[c * N + W - 1] &= xw.keep;  // (the d planes need none: nothing starts where A is zero)
+}
+
 template <int W, int P, int DET>
 __global__ __launch_bounds__(64 * kBatchWaves) void batch_gen_kernel(BNArgs a) {
     constexpr bool SETTLE = DET == kSettle, CYCLE = DET == kCycle;
@@ -648,6 +877,7 @@ __global__ __launch_bounds__(64 * kBatchWaves) void batch_gen_kernel(BNArgs a) {
 #pragma unroll
         for (int i = 0; i < N; ++i) T[i] = v[i];
     }
+    // (gen_generations<W, P, 1> spelled out: the instances of this kernel keep the code they were measured with)
     auto generation = [&]() {
         uint32_t s0[W], s1[W];
 #pragma unroll
@@ -758,6 +988,117 @@ hipError_t launch_gen(const BNArgs &a, int det, unsigned blocks, hipStream_t s) 
     else
         batch_gen_kernel<W, P, kNoDetector><<<blocks, 64 * kBatchWaves, 0, s>>>(a);
     return hipGetLastError();
+}
+
+// The onset form of Generations: batch_gen_kernel's cycle
+// detection plus the second phase of onset_body, every plane loaded, stepped
+// and compared.  One more state copy: W (1 + P) words.
+struct BMArgs {
+    BNArgs n;
+    int64_t *onset;
+};
+
+template <int W, int P>
+__global__ __launch_bounds__(64 * kBatchWaves) void batch_onset_gen_kernel(BMArgs o) {
+    constexpr int N = W * (1 + P);
+    const BNArgs &a = o.n;
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t u = (int64_t)blockIdx.x * kBatchWaves + wave_of_group();
+    if (u >= a.count) return;  // the whole wave
+    uint2 m = make_uint2(a.birth, a.survive);
+    if (a.rules) m = a.rules[u];
+    const TableRule rp = universe_rule(&m, 0);
+    const uint32_t states = m.x >> 16;
+    const uint32_t top = states > 2u ? states - 2u : 0u;
+    const uint32_t decays = states > 2u ? 0xFFFFFFFFu : 0u;
+    uint32_t L[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) L[p] = (top >> p) & 1u ? 0xFFFFFFFFu : 0u;
+
+    const int ny = a.ny;
+    const bool active = lane < ny;
+    const int up = !active ? lane : lane == 0 ? ny - 1 : lane - 1;
+    const int dn = !active ? lane : lane + 1 == ny ? 0 : lane + 1;
+    const int addr_up = up << 2, addr_dn = dn << 2;
+    const XWrap xw(a.nx, W);
+    const size_t at = ((size_t)u * (size_t)ny + (size_t)lane) * W;
+
+    uint32_t s[2 * N];  // v, and behind it the second chain of the search
+    uint32_t *const v = s, *const B = s + N;
+    auto load = [&]() {  // the universe's stored state, S_0 until the wave's one store
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[j] = active ? a.cells[at + j] : 0u;
+#pragma unroll
+        for (int p = 0; p < P; ++p)
+#pragma unroll
+            for (int j = 0; j < W; ++j)
+                v[W * (1 + p) + j] = active ? a.decay[(size_t)p * (size_t)a.plane + at + j] : 0u;
+    };
+    load();
+    uint32_t T[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        T[i] = v[i];
+        B[i] = 0u;
+    }
+    int gens = a.gens;
+    uint32_t power = 1, lam = 0;
+    const uint32_t known = __builtin_amdgcn_readfirstlane((uint32_t)a.period[u]);
+    const bool detect = known == 0u;
+    if (!detect) gens = (int)((uint32_t)gens % known);  // found in an earlier call
+    auto generation = [&]() { gen_generations<W, P, 1>(v, addr_up, addr_dn, xw, rp, decays, L); };
+    auto differs = [&](const uint32_t *than) {
+        uint32_t diff = 0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) diff |= v[i] ^ than[i];
+        return __builtin_amdgcn_ballot_w64(diff != 0u) != 0ull;
+    };
+    int rest = gens, g = 1;
+    if (detect) {
+        for (; g <= gens; ++g) {
+            generation();
+            ++lam;
+            if (!differs(T)) break;  // S_g == T in every plane: the minimal period is lam
+            if (lam == power) {
+#pragma unroll
+                for (int i = 0; i < N; ++i) T[i] = v[i];
+                power <<= 1;
+                lam = 0;
+            }
+        }
+        rest = 0;
+        if (g <= gens) {
+            load();
+#pragma unroll
+            for (int i = 0; i < N; ++i) B[i] = v[i];
+            for (uint32_t i = 0; i < lam; ++i) gen_generations<W, P, 1>(B, addr_up, addr_dn, xw, rp, decays, L);
+            const int bound = g - (int)lam;
+            int mu = bound;
+            for (int k = 0; k < bound; ++k) {
+                if (!differs(B)) {  // S_k == S_(k+lam)
+                    mu = k;
+                    break;
+                }
+                gen_generations<W, P, 2>(s, addr_up, addr_dn, xw, rp, decays, L);
+            }
+#pragma unroll
+            for (int i = 0; i < N; ++i) v[i] = T[i];  // S_g again
+            if (lane == 0) {
+                a.period[u] = (int64_t)lam;
+                a.found[u] = a.gen0 + g;
+                o.onset[u] = a.gen0 + mu;
+            }
+            rest = (int)((uint32_t)(gens - g) % lam);
+        }
+    }
+    for (g = 0; g < rest; ++g) generation();
+    if (!active) return;
+#pragma unroll
+    for (int j = 0; j < W; ++j) a.cells[at + j] = v[j];
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int j = 0; j < W; ++j) a.decay[(size_t)p * (size_t)a.plane + at + j] = v[W * (1 + p) + j];
 }
 
 // The data movement of the states: one thread per word position of the alive
@@ -935,6 +1276,39 @@ hipError_t launch_batch_trace(const BatchPlan &p, int64_t nx, int64_t ny, int64_
     }
 }
 
+hipError_t launch_batch_onset(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
+                              const RuleWords *rule, const uint32_t *rules, int64_t *period, int64_t *found,
+                              int64_t *onset, int64_t gen0, uint32_t *trace, hipStream_t s) {
+    if (p.tier != LIFE_BATCH_TIER_WAVE || gens < 1 || gens > INT32_MAX || !period || !found || !onset ||
+        (trace && count * gens > kBatchTraceEntries) || !grid_ok((count + kBatchWaves - 1) / kBatchWaves))
+        return hipErrorInvalidValue;
+    BOArgs o{};
+    BWArgs &a = o.w;
+    a.cells = cells;
+    a.count = count;
+    a.gen0 = gen0;
+    a.nx = (int32_t)nx;
+    a.ny = (int32_t)ny;
+    a.gens = (int32_t)gens;
+    if (rule) a.rule = *rule;
+    a.rules = reinterpret_cast<const uint2 *>(rules);
+    a.period = period;
+    a.found = found;
+    a.trace = trace;
+    o.onset = onset;
+    const int r = rules ? kSurveyPerUniverse : rule ? kSurveyTable : kSurveyConway;
+    const unsigned blocks = wave_blocks(count);
+    switch (p.words * 4 + r) {
+#define LIFE_BO(N) \
+    case N * 4 + kSurveyConway: return launch_onset<N, kSurveyConway>(o, blocks, s); \
+    case N * 4 + kSurveyTable: return launch_onset<N, kSurveyTable>(o, blocks, s); \
+    case N * 4 + kSurveyPerUniverse: return launch_onset<N, kSurveyPerUniverse>(o, blocks, s);
+        LIFE_BO(1) LIFE_BO(2) LIFE_BO(3) LIFE_BO(4)
+#undef LIFE_BO
+    default: return hipErrorInvalidValue;
+    }
+}
+
 namespace {
 
 hipError_t launch_group(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells, int64_t gens,
@@ -1043,6 +1417,42 @@ hipError_t launch_batch_gen(const BatchPlan &p, int64_t nx, int64_t ny, int64_t 
     case N * 8 + 4: return launch_gen<N, 4>(a, det, blocks, s);
         LIFE_BN(1) LIFE_BN(2) LIFE_BN(3) LIFE_BN(4)
 #undef LIFE_BN
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_batch_onset_gen(const BatchPlan &p, int64_t nx, int64_t ny, int64_t count, uint32_t *cells,
+                                  uint32_t *decay, int planes, int64_t gens, uint32_t birth, uint32_t survive,
+                                  uint32_t states, const uint32_t *rules, int64_t *period, int64_t *found,
+                                  int64_t *onset, int64_t gen0, hipStream_t s) {
+    if (p.tier != LIFE_BATCH_TIER_WAVE || gens < 1 || gens > INT32_MAX || !period || !found || !onset || !decay ||
+        !grid_ok((count + kBatchWaves - 1) / kBatchWaves))
+        return hipErrorInvalidValue;
+    BMArgs o{};
+    BNArgs &a = o.n;
+    a.cells = cells;
+    a.decay = decay;
+    a.plane = count * ny * p.words;
+    a.count = count;
+    a.gen0 = gen0;
+    a.nx = (int32_t)nx;
+    a.ny = (int32_t)ny;
+    a.gens = (int32_t)gens;
+    a.birth = birth | states << 16;
+    a.survive = survive;
+    a.rules = reinterpret_cast<const uint2 *>(rules);
+    a.period = period;
+    a.found = found;
+    o.onset = onset;
+    const unsigned blocks = wave_blocks(count);
+    switch (p.words * 8 + planes) {
+#define LIFE_BM(N, Q) \
+    case N * 8 + Q: \
+        batch_onset_gen_kernel<N, Q><<<blocks, 64 * kBatchWaves, 0, s>>>(o); \
+        return hipGetLastError();
+        LIFE_BM(1, 1) LIFE_BM(1, 2) LIFE_BM(1, 4) LIFE_BM(2, 1) LIFE_BM(2, 2) LIFE_BM(2, 4)
+        LIFE_BM(3, 1) LIFE_BM(3, 2) LIFE_BM(3, 4) LIFE_BM(4, 1) LIFE_BM(4, 2) LIFE_BM(4, 4)
+#undef LIFE_BM
     default: return hipErrorInvalidValue;
     }
 }

@@ -88,7 +88,7 @@ ABI_SYMBOLS = (
     "life_batch_set_rules", "life_batch_get_rules", "life_batch_cycles",
     "life_rule_parse_gen", "life_rule_format_gen", "life_batch_set_rule_gen", "life_batch_get_rule_gen",
     "life_batch_set_rules_gen", "life_batch_get_rules_gen", "life_batch_upload_states", "life_batch_gather_states",
-    "life_batch_census_gen", "life_batch_query_plan", "life_batch_population",
+    "life_batch_census_gen", "life_batch_query_plan", "life_batch_population", "life_batch_onsets",
 )
 GEN_MAX_STATES = 16  # LIFE_GEN_MAX_STATES
 BATCH_TIER_WAVE, BATCH_TIER_GROUP = 1, 2  # LIFE_BATCH_TIER_*
@@ -96,6 +96,7 @@ BATCH_TIERS = {BATCH_TIER_WAVE: "wave", BATCH_TIER_GROUP: "group"}
 BATCH_OPT_SETTLE = 1  # LIFE_BATCH_OPT_SETTLE
 BATCH_OPT_CYCLE = 3  # LIFE_BATCH_OPT_CYCLE (2 is unassigned)
 BATCH_OPT_POPULATION = 4  # LIFE_BATCH_OPT_POPULATION
+BATCH_OPT_ONSET = 5  # LIFE_BATCH_OPT_ONSET
 PATHS = {0: "none", 1: "onegen", 2: "tiles", 3: "flow", 5: "small", 6: "skip"}
 
 
@@ -245,6 +246,8 @@ def _lib():
             L.life_batch_census_gen.argtypes = [vp, P(i64), P(i64), P(u64)]
         if hasattr(L, "life_batch_population"):  # absent from builds that predate population traces
             L.life_batch_population.argtypes = [vp, i64, i64, P(u32), P(i64)]
+        if hasattr(L, "life_batch_onsets"):  # absent from builds that predate cycle onsets
+            L.life_batch_onsets.argtypes = [vp, P(i64)]
         if hasattr(L, "life_batch_query_plan"):  # absent from builds that predate it
             L.life_batch_query_plan.argtypes = [i64, i64] + [P(ctypes.c_int)] * 6
         L.life_tune.argtypes = [i32, i32, i32]
@@ -760,13 +763,15 @@ class LifeBatch:
     (:meth:`set_rules`; wave tier only).  ``settle``: stop a universe early once
     it repeats with period 1 or 2 (LIFE_BATCH_OPT_SETTLE; wave tier only).
     ``cycle``: find cycles of any period instead (LIFE_BATCH_OPT_CYCLE,
-    :meth:`cycles`; wave tier only, not together with ``settle``).
+    :meth:`cycles`; wave tier only, not together with ``settle``).  ``onset``:
+    with ``cycle``, also the exact generation at which each universe entered
+    its cycle (LIFE_BATCH_OPT_ONSET, :meth:`onsets`).
     ``population``: record every universe's live cells after each generation
     of a :meth:`step` call (LIFE_BATCH_OPT_POPULATION, :meth:`population`;
     DESIGN.md §5.14; both tiers, two-state rules only)."""
 
     def __init__(self, nx: int, ny: int, count: int, device: int = 0, rule=None, settle: bool = False, rules=None,
-                 cycle: bool = False, population: bool = False):
+                 cycle: bool = False, population: bool = False, onset: bool = False):
         self.nx, self.ny, self.count = int(nx), int(ny), int(count)
         self._h = ctypes.c_void_p()
         _check(_lib().life_batch_create(self.nx, self.ny, self.count, int(device), ctypes.byref(self._h)),
@@ -780,6 +785,8 @@ class LifeBatch:
             self.configure(BATCH_OPT_SETTLE, 1)
         if cycle:
             self.configure(BATCH_OPT_CYCLE, 1)
+        if onset:
+            self.configure(BATCH_OPT_ONSET, 1)
         if population:
             self.configure(BATCH_OPT_POPULATION, 1)
 
@@ -977,6 +984,16 @@ class LifeBatch:
         _check(_lib().life_batch_cycles(self._h, period.ctypes.data_as(i64p), found.ctypes.data_as(i64p)),
                "life_batch_cycles")
         return period, found
+
+    def onsets(self) -> np.ndarray:
+        """Per universe the generation at which its orbit entered the cycle
+        that :meth:`cycles` reports (LIFE_BATCH_OPT_ONSET, life_batch_onsets):
+        max(true onset, the generation the finding :meth:`step` call began at);
+        -1 where none was recorded (int64)."""
+        out = np.zeros(self.count, dtype=np.int64)
+        _check(_lib().life_batch_onsets(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
+               "life_batch_onsets")
+        return out
 
     def population(self, first: int = 0, n: int | None = None) -> np.ndarray:
         """The population trace of the last :meth:`step` call with

@@ -37,7 +37,17 @@ generation of the loop costs the same launches and readbacks).  Before any
 timing the trace of (b) over loop-gens generations is compared with the counts
 of (c).  read_s is life_batch_population of the whole trace, after the call.
 
+The onset lines, reported and not gated, one beside the
+cycle line and two more: 16384 soups of 32 x 32 at 35 % with step(4096) (the
+cycle line's batch), 262144 soups of 64 x 64 at 50 % with step(1024), and the
+same under Star Wars (B2/S345/C4).  Each measured two ways in one process,
+alternating within every repetition: LIFE_BATCH_OPT_CYCLE alone, and with
+LIFE_BATCH_OPT_ONSET beside it; the checksums and the cycle pairs of the two
+are compared.  Under LIFE_MI355X_LIB with a build that predates the option the
+lines hold the cycle-only figures alone (the A/B run against a parent build).
+
     python scripts/batch_bench.py --out profiles/batch/batch_bench.jsonl
+    python scripts/batch_bench.py --only onset --out profiles/batch/onset_bench.jsonl
     python scripts/batch_bench.py --only survey --out profiles/batch/survey_bench.jsonl
     python scripts/batch_bench.py --only gen --out profiles/batch/gen_bench.jsonl
     python scripts/batch_bench.py --only population --out profiles/batch/population_bench.jsonl
@@ -58,6 +68,8 @@ import life_mi355x as lm  # noqa: E402
 
 ROWS = [((32, 32), (1024, 16384, 262144)), ((64, 64), (1024, 16384, 262144)), ((128, 64), (1024, 16384, 262144)),
         ((500, 500), (256, 4096))]
+ONSET_ROWS = [((32, 32), 16384, 4096, 0.35, None), ((64, 64), 262144, 1024, 0.5, None),
+              ((64, 64), 262144, 1024, 0.5, "B2/S345/C4")]  # shape, count, generations, density, rule
 POPULATION_ROWS = [((64, 64), (16384, 262144)), ((128, 64), (16384, 262144)), ((500, 500), (4096,))]
 SEED = 1234
 
@@ -161,6 +173,40 @@ def population_row(nx, ny, count, gens, loop_gens, reps):
     return row
 
 
+def onset_row(nx, ny, count, gens, density, rule, reps):
+    """One onset line: cycle detection alone and with LIFE_BATCH_OPT_ONSET, alternating."""
+    has = hasattr(lm._lib(), "life_batch_onsets")
+    row = {"onset": True, "shape": [nx, ny], "count": count, "gens": gens, "density": density,
+           "rule": rule or "B3/S23", "option_in_build": has}
+    with lm.LifeBatch(nx, ny, count, rule=rule, cycle=True) as cyc:
+        ons = lm.LifeBatch(nx, ny, count, rule=rule, cycle=True, onset=True) if has else None
+        try:
+            c_t, o_t = [], []
+            for rep in range(reps + 1):  # the first is the warm-up
+                cyc.fill_random(SEED, density)
+                c_t.append(timed(lambda: cyc.step(gens), cyc.sync))
+                if ons:
+                    ons.fill_random(SEED, density)
+                    o_t.append(timed(lambda: ons.step(gens), ons.sync))
+            period = cyc.cycles()[0]
+            row.update({f"cycle_{k}": v for k, v in spread(c_t[1:]).items()})
+            row["cycle_share"] = float((period > 0).mean())
+            if ons:
+                sums = (lambda b: b.state_checksums() if (b.states > 2).any() else b.checksums())
+                if list(sums(cyc)) != list(sums(ons)) or any((x != y).any() for x, y in zip(cyc.cycles(), ons.cycles())):
+                    raise SystemExit(f"{nx}x{ny} x {count}: onset on and off disagree")
+                onsets = ons.onsets()
+                if ((onsets >= 0) != (period > 0)).any():
+                    raise SystemExit(f"{nx}x{ny} x {count}: an onset without a period, or a period without an onset")
+                row.update({f"onset_{k}": v for k, v in spread(o_t[1:]).items()})
+                row.update({"onset_over_cycle": row["onset_s"] / row["cycle_s"],
+                            "mean_onset": float(onsets[onsets >= 0].mean()), "max_onset": int(onsets.max())})
+        finally:
+            if ons:
+                ons.close()
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--gens", type=int, default=1024)
@@ -170,9 +216,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="the smallest count of every shape only")
     ap.add_argument("--loop-gens", type=int, default=32, help="generations of the population lines' host loop")
-    ap.add_argument("--only", choices=("all", "table", "settle", "survey", "gen", "population"), default="all",
-                    help="the shape table, the settle line, the survey lines, the Generations lines or the "
-                         "population lines alone")
+    ap.add_argument("--only", choices=("all", "table", "settle", "survey", "gen", "population", "onset"),
+                    default="all",
+                    help="the shape table, the settle line, the survey lines, the Generations lines, the "
+                         "population lines or the onset lines alone")
     a = ap.parse_args()
     out = open(a.out, "w") if a.out else None
 
@@ -222,6 +269,10 @@ def main():
               "settle_max_s": on[2], "settled_share": on[3], "cycle_s": cyc[0], "cycle_min_s": cyc[1],
               "cycle_max_s": cyc[2], "cycle_share": cyc[3], "settle_speedup": off[0] / on[0],
               "cycle_speedup": off[0] / cyc[0]})
+    for (nx, ny), count, gens, density, rule in ONSET_ROWS if a.only in ("all", "survey", "onset") else []:
+        # the onset option beside cycle detection (the first line: on the cycle line's batch)
+        emit(onset_row(nx, ny, min(count, 1024) if a.quick else count, gens, density, rule, a.reps))
+    if a.only in ("all", "survey"):
         # the price of a rule per universe: the uniform table kernel is the yardstick
         nx, ny, count, rule = 64, 64, 1024 if a.quick else 262144, "B36/S23"
         uni = batch_time(nx, ny, count, a.gens, a.reps, rule=rule)
