@@ -872,6 +872,43 @@ int life_batch_generation(life_batch *b, int64_t *generation);
 /* Waits for the batch's stream. */
 int life_batch_sync(life_batch *b);
 
+/* ---- which item a workgroup of a bit-tile launch runs (host only, no GPU) --
+ * One per-launch bit-tile launch as its launcher describes it: up to
+ * LIFE_TILE_MAX_REGIONS tile regions, tile columns [tx0, tx1) x tile rows
+ * [ty0, ty1) of window_rows - 2 m owned rows each, region k's items numbered
+ * from first[k] (first[0] = 0, first[nreg] = all of them): its ordinary tiles
+ * row-major, then the banded items of its last tile column when tx1 == btx1
+ * and nband > 0 (sub-column i in items of 64 >> bgsh[i] tile rows).  tail_ntx
+ * > 0 (one region): workgroups from tail_first on run half-height tiles over
+ * owned rows [tail_y, tail_yend), tail_ntx tile columns from tail_tx0 per tile
+ * row, listed the same way.  xcd_n: the workgroups renumbered into per-XCD
+ * row-major runs (0: dispatch order). */
+#define LIFE_TILE_MAX_REGIONS 4
+typedef struct life_tile_launch {
+    int32_t nreg, nband, m, window_rows;
+    int64_t tx0[LIFE_TILE_MAX_REGIONS], tx1[LIFE_TILE_MAX_REGIONS], ty0[LIFE_TILE_MAX_REGIONS],
+        ty1[LIFE_TILE_MAX_REGIONS], first[LIFE_TILE_MAX_REGIONS + 1];
+    int32_t bgsh[2];
+    int64_t btx1;
+    int64_t tail_first, tail_y, tail_yend, tail_ntx, tail_tx0;
+    int64_t xcd_n;
+} life_tile_launch;
+#define LIFE_TILE_NONE 0      /* a workgroup beyond the items: does nothing */
+#define LIFE_TILE_FULL 1      /* ordinary tile (tx, ty) of `region` */
+#define LIFE_TILE_BAND 2      /* banded item `band_item` of `region` (tile rows [ty0, ty0 + rows)) */
+#define LIFE_TILE_TAIL 3      /* half-height tile: column tx, tile row ty of the tail's `rows` */
+#define LIFE_TILE_TAIL_BAND 4 /* banded item `band_item` of the tail */
+typedef struct life_tile_item {
+    int32_t kind, region, tx, ty, ty0, rows;
+    int64_t band_item;
+} life_tile_item;
+/* The decode the kernels run (32-bit arithmetic on constants made once per
+ * launch), replayed on the CPU: out[i] = the item of workgroup wg[i], 0 <=
+ * wg[i] < 2^31.  LIFE_EINVAL, with a message: a description that is
+ * inconsistent or whose counts leave the 32-bit range the kernels work in
+ * (such a launch fails on the device path too). */
+int life_tile_decode_query(const life_tile_launch *launch, const int64_t *wg, int64_t n, life_tile_item *out);
+
 #ifdef __cplusplus
 }
 #endif

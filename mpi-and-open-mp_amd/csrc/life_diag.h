@@ -18,8 +18,11 @@ namespace {
 // life_debug_wg_trace copies it out.
 #if LIFE_WG_TRACE
 __device__ uint64_t g_wg_trace[16 * 65536];
-__device__ __forceinline__ void wg_trace(int what) {  // 0: start, k >= 1: end of tile k
-    if (threadIdx.x != 0 || blockIdx.x >= 65536 || what > 14) return;
+// (tid: the stamping thread.  The per-launch bit tiles stamp three phases of their one item from thread
+// 64, the first lane of a wave that holds no ghost rows at m <= R, as what = 2, 3, 4: slots 3-5, which
+// those kernels use for nothing else -- they end one item, what = 1; scripts/wg_trace.py reads them so)
+__device__ __forceinline__ void wg_trace(int what, unsigned tid = 0) {  // 0: start, k >= 1: end of tile k
+    if (threadIdx.x != tid || blockIdx.x >= 65536 || what > 14) return;
     uint64_t *t = g_wg_trace + 16 * blockIdx.x;
     t[what == 0 ? 0 : what + 1] = wall_clock64();
     if (what == 0) {
@@ -29,7 +32,7 @@ __device__ __forceinline__ void wg_trace(int what) {  // 0: start, k >= 1: end o
     }
 }
 #else
-__device__ __forceinline__ void wg_trace(int) {}
+__device__ __forceinline__ void wg_trace(int, unsigned = 0) {}
 #endif
 }  // namespace
 }  // namespace life

@@ -29,6 +29,7 @@
 #include "life_bitops.h"
 #include "life_diag.h"
 #include "life_env.h"
+#include "life_tile_decode.h"
 
 #include <hip/hip_ext.h>
 
@@ -407,7 +408,12 @@ struct TArgs {
     // deep-halo pass (Extend::x, bit): the lanes holding the apron pairs -1
     // and W store them too
     int32_t xext;
+    // the item decode's constants, made from the fields above once per
+    // launch (tile_args_seal, life_tile_decode.h): the kernels find their
+    // item in 32-bit arithmetic and read none of the region fields
+    TileDec d;
 };
+static_assert(kMaxRegions == kTdMaxRegions && kMaxBands == kTdMaxBands, "life_tile_decode.h");
 
 // Census instances of the bit tiles (LIFE_OPT_POPULATION): a
 // tile also counts, after every generation of its pass, the live cells it
@@ -488,6 +494,16 @@ struct XchB {
 #ifndef LIFE_FAST_WRAP
 #define LIFE_FAST_WRAP 1
 #endif
+// LIFE_TILE_STRAIGHT (compile time, A/B): a plain tile's wave decides once
+// whether its R window rows cross the periodic seam and whether it stores all
+// of its R rows; when not / so -- all but the waves at a window's ends and the
+// first and last tile rows of a launch -- the loads and the stores are R
+// instructions in one basic block each, the row base walked by the pitch in
+// scalar registers (0: a wrap test per loaded row, two range tests per stored
+// row; profiles/tilehead).
+#ifndef LIFE_TILE_STRAIGHT
+#define LIFE_TILE_STRAIGHT 1
+#endif
 
 //
 // ACT (tskip kernels, LIFE_OPT_SKIP_DEAD): a plain tile also notes, per row it
@@ -507,9 +523,9 @@ struct XchB {
 // nothing when off, as ACT.
 template <int R, bool WRAPX, bool WRAPY, int FLOW, int NW, bool BAND = false, class RP = ConwayRule, bool ACT = false,
           bool POP = false>
-__device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in, uint8_t *out, int64_t tx,
-                                              int64_t ty, XchB<NW> &xb, int gsh = 6, int nb = 1,
-                                              int64_t ybase = 0, int64_t yend = -1, int64_t org = 0, int own = 62,
+__device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in, uint8_t *out, int tx,
+                                              int ty, XchB<NW> &xb, int gsh = 6, int nb = 1,
+                                              int ybase = 0, int yend = -1, int org = 0, int own = 62,
                                               const RP &rule = RP{}, uint32_t *act = nullptr,
                                               const PopArgs *pa = nullptr, uint32_t *pl = nullptr) {
     XchP<NW> &xch = xb.s;
@@ -524,22 +540,26 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
     const int gl = BAND ? lane >> gsh : 0;                  // this lane's band (tile row ty + gl)
     const int pin = BAND ? lane & ((1 << gsh) - 1) : lane;  // lane within its group
     // pair column of this lane (BAND: the sub-column's pairs start at org; tx is not used)
-    const int64_t j = (BAND ? org : tx * 62) + pin - 1;
-    int64_t jl;
+    // Column and row indices are 32-bit: pair columns up to W + 62 and rows
+    // up to h + 17 T + NW R are below 2^31 for every launch the host lets
+    // through (tile_args_seal); only row x pitch byte offsets are 64-bit.
+    const int W = (int)a.W, h = (int)a.h;
+    const int j = (BAND ? org : tx * 62) + pin - 1;
+    int jl;
     if (WRAPX) {
         // j lies in [-1, W + 62): one conditional add / subtract when W >= 64
-        // (a 64-bit remainder per lane otherwise, ~100 VALU per tile)
-        if (LIFE_FAST_WRAP && a.W >= 64) {
-            jl = j < 0 ? j + a.W : (j >= a.W ? j - a.W : j);
+        // (a remainder per lane otherwise)
+        if (LIFE_FAST_WRAP && W >= 64) {
+            jl = j < 0 ? j + W : (j >= W ? j - W : j);
         } else {
-            jl = j % a.W;
-            if (jl < 0) jl += a.W;
+            jl = j % W;
+            if (jl < 0) jl += W;
         }
     } else {
-        jl = j > a.W ? a.W : j;  // pairs -1 .. W hold cells / apron; beyond: clamp (never stored)
+        jl = j > W ? W : j;  // pairs -1 .. W hold cells / apron; beyond: clamp (never stored)
     }
-    const uint32_t voff = (uint32_t)(a.xoff + 8 * jl);
-    const int64_t y0 = ybase + ty * T - K + (int64_t)wi * R;  // owned row of register row 0 (>= -K)
+    const uint32_t voff = (uint32_t)a.xoff + 8u * (uint32_t)jl;
+    const int y0 = ybase + ty * T - K + wi * R;  // owned row of register row 0 (>= -K)
     // Row pointers are walked: with a periodic y axis the walk wraps at h;
     // with an apron the last tile's window may run past the apron row h+K-1
     // into the allocation slack below the buffer (kTemporalSlackRows; those
@@ -547,21 +567,20 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
     const uint8_t *row0 = in + a.ya * a.pitch;  // owned row 0
     uint32_t ve[R], vo[R];
     {
-        int64_t y = y0 + (BAND ? (int64_t)(gl < nb ? gl : nb - 1) * T : 0);  // bands: per-lane rows
+        int y = y0 + (BAND ? (gl < nb ? gl : nb - 1) * T : 0);  // bands: per-lane rows
         if (WRAPY) {
             // y lies in [-K, h + 16 T + NW R) (a band lane adds gl T, gl < 16):
             // one conditional add / subtract when h exceeds that margin with
-            // room to spare (a 64-bit remainder otherwise)
-            if (LIFE_FAST_WRAP && a.h > 65 * (int64_t)(NW * R)) {
-                y = y < 0 ? y + a.h : (y >= a.h ? y - a.h : y);
+            // room to spare (a remainder otherwise)
+            if (LIFE_FAST_WRAP && h > 65 * (NW * R)) {
+                y = y < 0 ? y + h : (y >= h ? y - h : y);
             } else {
-                y %= a.h;
-                if (y < 0) y += a.h;
+                y %= h;
+                if (y < 0) y += h;
             }
         }
-        const uint8_t *p = row0 + y * a.pitch;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
+        const uint8_t *p = row0 + (int64_t)y * a.pitch;
+        auto load_row = [&](int r) {
             uint64_t q;
             if (FLOW)
                 q = __hip_atomic_load(reinterpret_cast<uint64_t *>(const_cast<uint8_t *>(p) + voff),
@@ -570,12 +589,30 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
                 q = *reinterpret_cast<const uint64_t *>(p + voff);
             ve[r] = (uint32_t)q;
             vo[r] = (uint32_t)(q >> 32);
-            ++y;
-            if (WRAPY && y == a.h) {
-                y = 0;
-                p = row0;
-            } else {
+        };
+        // A plain tile's rows are wave-uniform.  Unless the wave's R rows cross
+        // the periodic seam (the first and last tile rows of a launch only) the
+        // row base is walked by the pitch with no test per row: the R loads in
+        // one basic block (LIFE_TILE_STRAIGHT, tests/test_isa_tile_head.py).
+        // Without WRAPY the walk never wraps (the window may run into the
+        // slack rows below the buffer, see above).
+        if (LIFE_TILE_STRAIGHT && !BAND && (!WRAPY || y + R <= h)) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                load_row(r);
                 p += a.pitch;
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                load_row(r);
+                ++y;
+                if (WRAPY && y == h) {
+                    y = 0;
+                    p = row0;
+                } else {
+                    p += a.pitch;
+                }
             }
         }
     }
@@ -604,6 +641,10 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
     const uint32_t rm_s = POP && !BAND ? (uint32_t)__builtin_amdgcn_readfirstlane((int)pop_rows(y0)) : 0u;
     if (wi == 0 || wi == NW - 1)  // the dead slots (ordered by the first barrier below)
         for (int q = 0; q < 16; ++q) xch[q >> 3][wi == 0 ? 0 : NW + 1][q & 7][lane] = 0u;
+    if (LIFE_WG_TRACE && !FLOW) {  // phase stamps of the per-launch tiles (scripts/wg_trace.py): window loaded
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wg_trace(2, 64);
+    }
     for (int g = 0; g < a.m; ++g) {
         const int par = g & 1;
         uint32_t pe0, pe1, po0, po1, ce0, ce1, co0, co1;
@@ -703,6 +744,7 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
             if (l3 == 0) pl[g * NW + wi] = c;
         }
     }
+    if (LIFE_WG_TRACE && !FLOW) wg_trace(3, 64);  // generations done
     // window rows [K, NW*R - K) are the tile's owned rows [ty*T, ty*T + T);
     // this wave's share of them (a half-height tile's ghost rows may span more
     // than one wave: K > R)
@@ -718,37 +760,53 @@ __device__ __forceinline__ void tile_body_bit(const TArgs &a, const uint8_t *in,
     asm volatile("" : "+v"(lane2));
     const int gl2 = BAND ? lane2 >> gsh : 0;
     const int pin2 = BAND ? lane2 & ((1 << gsh) - 1) : lane2;
-    const int64_t j2 = (BAND ? org : tx * 62) + pin2 - 1;
+    const int j2 = (BAND ? org : tx * 62) + pin2 - 1;
     const bool st = (BAND ? (pin2 >= 1 && pin2 <= own && gl2 < nb)
-                          : (lane2 >= 1 && lane2 <= 62 && j2 < a.W)) ||
-                    (!WRAPX && a.xext && (!BAND || gl2 < nb) && (j2 == -1 || j2 == a.W));
-    const int64_t yb = y0 + (BAND ? (int64_t)(gl2 < nb ? gl2 : 0) * T : 0);  // this lane's band
-    const int64_t ylim = yend >= 0 ? yend : a.h;  // half tiles of a region stop at its last row
+                          : (lane2 >= 1 && lane2 <= 62 && j2 < (int)a.W)) ||
+                    (!WRAPX && a.xext && (!BAND || gl2 < nb) && (j2 == -1 || j2 == (int)a.W));
+    const int yb = y0 + (BAND ? (gl2 < nb ? gl2 : 0) * T : 0);  // this lane's band
+    const int ylim = yend >= 0 ? yend : (int)a.h;  // half tiles of a region stop at its last row
     uint8_t *q = out + (a.ya + yb + r0) * a.pitch + voff;
+    auto store_row = [&](int r) {
+        const uint64_t v = (uint64_t)ve[r] | ((uint64_t)vo[r] << 32);
+        if (FLOW == 1)
+            __hip_atomic_store(reinterpret_cast<uint64_t *>(q), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else
+            *reinterpret_cast<uint64_t *>(q) = v;
+    };
     // ACT: the row masks (life_act.h) of what this wave stores in map rows ar0 and ar0 + 1, wave-uniform
     uint32_t am[2][kActWords] = {};
-    const int64_t ar0 = ACT ? (yb + r0) / kActRows : 0;
-    const int llast = ACT ? (int)min((int64_t)kActPairs, a.W - tx * kActPairs) : 0;  // lane of the last owned pair
+    const int ar0 = ACT ? (yb + r0) / kActRows : 0;
+    const int llast = ACT ? min(kActPairs, (int)a.W - tx * kActPairs) : 0;  // lane of the last owned pair
+    // A plain tile's wave that holds no ghost row and ends inside the stored
+    // rows (every wave but those at a window's ends, in every tile row but a
+    // cut last one) stores its R rows under one lane mask, in one basic
+    // block; the others test each row (a wave of ghost rows only: none).
+    if (LIFE_TILE_STRAIGHT && !BAND && !ACT && r0 == 0 && r1 == R && yb + R <= ylim) {
+        if (st) {
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (r < r0 || r >= r1) continue;
-        if (st && yb + r < ylim) {
-            const uint64_t v = (uint64_t)ve[r] | ((uint64_t)vo[r] << 32);
-            if (FLOW == 1)
-                __hip_atomic_store(reinterpret_cast<uint64_t *>(q), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else
-                *reinterpret_cast<uint64_t *>(q) = v;
+            for (int r = 0; r < R; ++r) {
+                store_row(r);
+                q += a.pitch;
+            }
         }
-        if (ACT && yb + r < ylim) {  // (uniform: every lane of the wave is here)
-            const unsigned long long nz = __ballot(st && (ve[r] | vo[r]) != 0u);
-            const uint32_t bit = 1u << ((yb + r) % kActRows);
-            const int k = (yb + r) / kActRows == ar0 ? 0 : 1;
-            if (nz) am[k][kActAny] |= bit;
-            if ((nz >> 1) & 1ull) am[k][kActFirst] |= bit;  // lane 1 holds pair 62 tx
-            if ((nz >> llast) & 1ull) am[k][kActLast] |= bit;
+    } else if (r0 < r1) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (r < r0 || r >= r1) continue;
+            if (st && yb + r < ylim) store_row(r);
+            if (ACT && yb + r < ylim) {  // (uniform: every lane of the wave is here)
+                const unsigned long long nz = __ballot(st && (ve[r] | vo[r]) != 0u);
+                const uint32_t bit = 1u << ((yb + r) % kActRows);
+                const int k = (yb + r) / kActRows == ar0 ? 0 : 1;
+                if (nz) am[k][kActAny] |= bit;
+                if ((nz >> 1) & 1ull) am[k][kActFirst] |= bit;  // lane 1 holds pair 62 tx
+                if ((nz >> llast) & 1ull) am[k][kActLast] |= bit;
+            }
+            q += a.pitch;
         }
-        q += a.pitch;
     }
+    if (LIFE_WG_TRACE && !FLOW) wg_trace(4, 64);  // stores issued
     if (ACT && lane2 == 0) {
         // stored rows are owned rows (< h): a nonzero mask's map row exists.  Waves (24 rows) and
         // vertically adjacent tiles share 32-row words: OR, not store.
@@ -944,16 +1002,16 @@ constexpr int bit_wpe(int NW, int R) { return NW == 16 ? (R <= 16 ? 8 : 4) : (R 
 // as the items of sub-column 0 (ceil(rows / B_0), B_i = 64 >> bgsh[i] tile
 // rows each), then those of sub-column 1.  Wave-uniform throughout.
 template <int RS, bool WRAPX, bool WRAPY, int NW, class RP = ConwayRule, bool POP = false>
-__device__ __forceinline__ void band_item(const TArgs &a, int64_t i, int64_t ty0, int64_t rows, XchB<NW> &xch,
-                                          int64_t ybase = 0, int64_t yend = -1, const RP &rule = RP{},
-                                          const PopArgs *pa = nullptr, uint32_t *pl = nullptr) {
-    const int64_t n0 = (rows + (64 >> a.bgsh[0]) - 1) >> (6 - a.bgsh[0]);
+__device__ __forceinline__ void band_item(const TArgs &a, int i, int ty0, int rows, XchB<NW> &xch, int ybase = 0,
+                                          int yend = -1, const RP &rule = RP{}, const PopArgs *pa = nullptr,
+                                          uint32_t *pl = nullptr) {
+    const int n0 = (rows + (64 >> a.bgsh[0]) - 1) >> (6 - a.bgsh[0]);
     const bool second = a.nband > 1 && i >= n0;
     if (second) i -= n0;
     const int gsh = second ? a.bgsh[1] : a.bgsh[0], own = second ? a.bown[1] : a.bown[0];
-    const int64_t org = second ? a.borg[1] : a.borg[0];
-    const int64_t B = 64 >> gsh, t = i * B;  // first tile row of the item within the region
-    const int nb = (int)(rows - t < B ? rows - t : B);
+    const int org = (int)(second ? a.borg[1] : a.borg[0]);
+    const int B = 64 >> gsh, t = i * B;  // first tile row of the item within the region
+    const int nb = rows - t < B ? rows - t : B;
     if (POP)
         tile_body_bit<RS, WRAPX, WRAPY, 0, NW, true, RP, false, POP>(a, a.in, a.out, 0, ty0 + t, xch, gsh, nb, ybase,
                                                                      yend, org, own, rule, nullptr, pa, pl);
@@ -962,110 +1020,47 @@ __device__ __forceinline__ void band_item(const TArgs &a, int64_t i, int64_t ty0
                                                      rule);
 }
 
-// Item i of the tail (TArgs::tail_*): RS rows per wave, tile rows of TS =
-// NW RS - 2m owned rows from owned row tail_y, the last one stopping at
-// tail_yend; tail_ntx - 1 ordinary tiles per tile row from column tail_tx0,
-// then the banded items of the last tile column (band_item), or tail_ntx
-// tiles per row without it.  (Round 5's half tiles spanned
-// the last column as full-width tiles; banded they take (64 - o - 2) / 64
-// fewer lanes there.)
-template <int RS, bool WRAPX, bool WRAPY, int NW, class RP = ConwayRule, bool POP = false>
-__device__ __forceinline__ void tail_item(const TArgs &a, int64_t i, XchB<NW> &xch, const RP &rule = RP{},
-                                          const PopArgs *pa = nullptr, uint32_t *pl = nullptr) {
-    const int64_t TS = (int64_t)NW * RS - 2 * a.m, y0 = a.tail_y, yend = a.tail_yend;
-    const int64_t rows = (yend - y0 + TS - 1) / TS;
-    const bool band = a.nband > 0 && a.tail_tx0 + a.tail_ntx == a.btx1;
-    const int64_t ntxs = a.tail_ntx - (band ? 1 : 0), nfull = ntxs * rows;
-    if (POP) {
-        if (i < nfull)
-            tile_body_bit<RS, WRAPX, WRAPY, 0, NW, false, RP, false, POP>(a, a.in, a.out, a.tail_tx0 + i % ntxs,
-                                                                          i / ntxs, xch, 6, 1, y0, yend, 0, 62, rule,
-                                                                          nullptr, pa, pl);
+// One workgroup per item (life_tile_decode.h: which one, from the launch's
+// constants in 32-bit arithmetic): a tile, a banded item, or an item of the
+// tail (TArgs::tail_*) -- RS = R / 2 rows per wave, tile rows of TS = NW RS -
+// 2m owned rows from owned row tail_y, the last one stopping at tail_yend;
+// per tile row the ordinary tiles from column tail_tx0, then the banded items
+// of the last tile column.  (Round 5's half tiles spanned the last column as
+// full-width tiles; banded they take (64 - o - 2) / 64 fewer lanes there.)
+// One call site per kind: four copies of the generation loop, as before.
+template <int R, bool WRAPX, bool WRAPY, int NW, class RP, bool POP = false>
+__device__ __forceinline__ void tstep_bit_items(const TArgs &a, XchB<NW> &xch, const RP &rule,
+                                                const PopArgs *pa = nullptr, uint32_t *pl = nullptr) {
+    wg_trace(0);
+    const TileItem it = tile_decode(a.d, blockIdx.x);
+    if (it.kind == kTileNone) return;  // whole workgroup
+    const bool tail = it.kind == kTileTail || it.kind == kTileTailBand;
+    const int ybase = tail ? (int)a.tail_y : 0, yend = tail ? (int)a.tail_yend : -1;
+    if (it.kind == kTileFull) {
+        if (POP)
+            tile_body_bit<R, WRAPX, WRAPY, 0, NW, false, RP, false, POP>(a, a.in, a.out, it.tx, it.ty, xch, 6, 1, 0, -1,
+                                                                         0, 62, rule, nullptr, pa, pl);
         else
-            band_item<RS, WRAPX, WRAPY, NW, RP, POP>(a, i - nfull, 0, rows, xch, y0, yend, rule, pa, pl);
-        return;
+            tile_body_bit<R, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, it.tx, it.ty, xch, 6, 1, 0, -1, 0, 62, rule);
+    } else if (it.kind == kTileBand) {
+        band_item<R, WRAPX, WRAPY, NW, RP, POP>(a, (int)it.bi, it.ty0, it.rows, xch, 0, -1, rule, pa, pl);
+    } else if (it.kind == kTileTail) {
+        if (POP)
+            tile_body_bit<R / 2, WRAPX, WRAPY, 0, NW, false, RP, false, POP>(a, a.in, a.out, it.tx, it.ty, xch, 6, 1,
+                                                                             ybase, yend, 0, 62, rule, nullptr, pa, pl);
+        else
+            tile_body_bit<R / 2, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, it.tx, it.ty, xch, 6, 1, ybase, yend, 0, 62,
+                                                      rule);
+    } else {
+        band_item<R / 2, WRAPX, WRAPY, NW, RP, POP>(a, (int)it.bi, 0, it.rows, xch, ybase, yend, rule, pa, pl);
     }
-    if (i < nfull)
-        tile_body_bit<RS, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, a.tail_tx0 + i % ntxs, i / ntxs, xch, 6, 1, y0, yend,
-                                              0, 62, rule);
-    else
-        band_item<RS, WRAPX, WRAPY, NW>(a, i - nfull, 0, rows, xch, y0, yend, rule);
+    wg_trace(1);
 }
 
-// One workgroup per tile (or banded item / partial-height tail tile).
 template <int R, bool WRAPX, bool WRAPY, int NW>
 __global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tstep_bit_kernel(TArgs a) {
     __shared__ XchB<NW> xch;
-    wg_trace(0);
-    int64_t wg = blockIdx.x;
-    if (wg < a.xcd_n) {
-        // the dispatcher deals blocks round-robin over the 8 XCDs: XCD x runs
-        // blocks 8k + x, here items first_x + k, so the tiles beside and below
-        // a tile share its XCD's L2 (their common ghost rows and boundary
-        // lines are fetched once); a bijection of [0, xcd_n)
-        const int64_t n = a.xcd_n, x = wg & 7, k = wg >> 3, per = n >> 3, rem = n & 7;
-        wg = (x < rem ? x * (per + 1) : rem * (per + 1) + (x - rem) * per) + k;
-    }
-    if (a.tail_ntx > 0 && wg >= a.tail_first) {
-        tail_item<R / 2, WRAPX, WRAPY, NW>(a, wg - a.tail_first, xch);
-        wg_trace(1);
-        return;
-    }
-    const int64_t nwg = a.first[a.nreg];
-    if (wg >= nwg) return;  // whole workgroup
-    int k = 0;
-    while (k + 1 < a.nreg && wg >= a.first[k + 1]) ++k;
-    const int64_t wr = wg - a.first[k];
-    const bool bands = a.nband > 0 && a.tx1[k] == a.btx1;
-    const int64_t ntx = a.tx1[k] - a.tx0[k] - (bands ? 1 : 0);
-    const int64_t nfull = ntx * (a.ty1[k] - a.ty0[k]);
-    if (wr < nfull) {
-        const int64_t tx = a.tx0[k] + wr % ntx, ty = a.ty0[k] + wr / ntx;
-        tile_body_bit<R, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, tx, ty, xch);
-    } else {
-        band_item<R, WRAPX, WRAPY, NW>(a, wr - nfull, a.ty0[k], a.ty1[k] - a.ty0[k], xch);
-    }
-    wg_trace(1);
-}
-
-
-// tstep_bit_kernel's item dispatch again, under a rule policy, for the
-// table-rule kernel below (a twin for the reason given at step_body: the
-// B3/S23 instances keep their own text and so their code).
-template <int R, bool WRAPX, bool WRAPY, int NW, class RP, bool POP = false>
-__device__ __forceinline__ void tstep_bit_body(const TArgs &a, XchB<NW> &xch, const RP &rule,
-                                               const PopArgs *pa = nullptr, uint32_t *pl = nullptr) {
-    wg_trace(0);
-    int64_t wg = blockIdx.x;
-    if (wg < a.xcd_n) {  // per-XCD row-major runs, as tstep_bit_kernel
-        const int64_t n = a.xcd_n, x = wg & 7, k = wg >> 3, per = n >> 3, rem = n & 7;
-        wg = (x < rem ? x * (per + 1) : rem * (per + 1) + (x - rem) * per) + k;
-    }
-    if (a.tail_ntx > 0 && wg >= a.tail_first) {
-        tail_item<R / 2, WRAPX, WRAPY, NW, RP, POP>(a, wg - a.tail_first, xch, rule, pa, pl);
-        wg_trace(1);
-        return;
-    }
-    const int64_t nwg = a.first[a.nreg];
-    if (wg >= nwg) return;  // whole workgroup
-    int k = 0;
-    while (k + 1 < a.nreg && wg >= a.first[k + 1]) ++k;
-    const int64_t wr = wg - a.first[k];
-    const bool bands = a.nband > 0 && a.tx1[k] == a.btx1;
-    const int64_t ntx = a.tx1[k] - a.tx0[k] - (bands ? 1 : 0);
-    const int64_t nfull = ntx * (a.ty1[k] - a.ty0[k]);
-    if (wr < nfull) {
-        const int64_t tx = a.tx0[k] + wr % ntx, ty = a.ty0[k] + wr / ntx;
-        if (POP)
-            tile_body_bit<R, WRAPX, WRAPY, 0, NW, false, RP, false, POP>(a, a.in, a.out, tx, ty, xch, 6, 1, 0, -1, 0,
-                                                                         62, rule, nullptr, pa, pl);
-        else
-            tile_body_bit<R, WRAPX, WRAPY, 0, NW>(a, a.in, a.out, tx, ty, xch, 6, 1, 0, -1, 0, 62, rule);
-    } else {
-        band_item<R, WRAPX, WRAPY, NW, RP, POP>(a, wr - nfull, a.ty0[k], a.ty1[k] - a.ty0[k], xch, 0, -1, rule, pa,
-                                                pl);
-    }
-    wg_trace(1);
+    tstep_bit_items<R, WRAPX, WRAPY, NW>(a, xch, ConwayRule{});
 }
 
 // The same tiles with B3/S23 in 7 gates per dword (ConwayRule7, life_bitops.h;
@@ -1080,7 +1075,7 @@ __device__ __forceinline__ void tstep_bit_body(const TArgs &a, XchB<NW> &xch, co
 template <int R, bool WRAPX, bool WRAPY, int NW>
 __global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tstep_bit7_kernel(TArgs a) {
     __shared__ XchB<NW> xch;
-    tstep_bit_body<R, WRAPX, WRAPY, NW>(a, xch, ConwayRule7{});
+    tstep_bit_items<R, WRAPX, WRAPY, NW>(a, xch, ConwayRule7{});
 }
 
 // The same tiles under a table rule (life_dev_set_rule): the tail is 25
@@ -1107,7 +1102,7 @@ struct RTArgs {
 template <int R, bool WRAPX, bool WRAPY, int NW>
 __global__ __launch_bounds__(64 * NW, LIFE_RULE_WPE) void trule_bit_kernel(RTArgs a) {
     __shared__ XchB<NW> xch;
-    tstep_bit_body<R, WRAPX, WRAPY, NW>(a.t, xch, TableRule(a.w));
+    tstep_bit_items<R, WRAPX, WRAPY, NW>(a.t, xch, TableRule(a.w));
 }
 
 // The census instances of both (PopArgs): the same items through the same
@@ -1120,7 +1115,7 @@ template <int R, bool WRAPX, bool WRAPY, int NW>
 __global__ __launch_bounds__(64 * NW, LIFE_POP_WPE) void tpop_bit_kernel(PTArgs a) {
     __shared__ XchB<NW> xch;
     __shared__ uint32_t pl[kPopGens * NW];
-    tstep_bit_body<R, WRAPX, WRAPY, NW, ConwayRule, true>(a.t, xch, ConwayRule{}, &a.p, pl);
+    tstep_bit_items<R, WRAPX, WRAPY, NW, ConwayRule, true>(a.t, xch, ConwayRule{}, &a.p, pl);
 }
 struct RPTArgs {
     TArgs t;
@@ -1131,7 +1126,7 @@ template <int R, bool WRAPX, bool WRAPY, int NW>
 __global__ __launch_bounds__(64 * NW, LIFE_RULE_WPE) void tpop_rule_kernel(RPTArgs a) {
     __shared__ XchB<NW> xch;
     __shared__ uint32_t pl[kPopGens * NW];
-    tstep_bit_body<R, WRAPX, WRAPY, NW, TableRule, true>(a.t, xch, TableRule(a.w), &a.p, pl);
+    tstep_bit_items<R, WRAPX, WRAPY, NW, TableRule, true>(a.t, xch, TableRule(a.w), &a.p, pl);
 }
 
 // ---- skip-dead passes (LIFE_OPT_SKIP_DEAD; DESIGN.md 5.9, life_act.h)
@@ -1183,16 +1178,19 @@ struct KArgs {
     const uint8_t *cls;  // class per tile, row-major over ntx x nty
     uint32_t *act;       // the output buffer's map, zeroed
     int64_t ntx, nty;
+    uint32_t ntx_mul;    // tile_recip(ntx): the tile of a workgroup without a division
 };
 template <int R, int NW, class RP, bool POP = false>
 __device__ __forceinline__ void tskip_body(const KArgs &k, XchB<NW> &xch, const RP &rule,
                                            const PopArgs *pa = nullptr, uint32_t *pl = nullptr) {
     const TArgs &a = k.t;
-    const int64_t wg = blockIdx.x;
-    if (wg >= k.ntx * k.nty) return;
+    const uint32_t wg = blockIdx.x;  // (tiles < 2^31: launch_tskip)
+    if (wg >= (uint32_t)k.ntx * (uint32_t)k.nty) return;
     const int c = __builtin_amdgcn_readfirstlane((int)k.cls[wg]);
     if (c == kActSkip) return;  // whole workgroup, uniform, before any barrier
-    const int64_t tx = wg % k.ntx, ty = wg / k.ntx;
+    uint32_t qy, rx;
+    tile_divmod(wg, (uint32_t)k.ntx, k.ntx_mul, qy, rx);
+    const int tx = (int)rx, ty = (int)qy;
     if (c == kActClear) {
         const int64_t T = (int64_t)NW * R - 2 * a.m;
         const int64_t ya = ty * T, yb = act_own_end(ty, T, a.h);
@@ -1265,19 +1263,10 @@ template <int R, int GK, bool WRAPX, bool WRAPY, int NW>
 __global__ __launch_bounds__(64 * NW, LIFE_BYTE_WPE) void tstep_byte_kernel(TArgs a) {
     __shared__ Xch<NW> xch;
     wg_trace(0);
-    int64_t wg = blockIdx.x;
-    if (wg < a.xcd_n) {  // per-XCD row-major runs, as tstep_bit_kernel
-        const int64_t n = a.xcd_n, x = wg & 7, k = wg >> 3, per = n >> 3, rem = n & 7;
-        wg = (x < rem ? x * (per + 1) : rem * (per + 1) + (x - rem) * per) + k;
-    }
-    const int64_t nwg = a.first[a.nreg];
-    if (wg >= nwg) return;
-    int k = 0;
-    while (k + 1 < a.nreg && wg >= a.first[k + 1]) ++k;
-    const int64_t wr = wg - a.first[k];
-    const int64_t ntx = a.tx1[k] - a.tx0[k];
-    const int64_t tx = a.tx0[k] + wr % ntx, ty = a.ty0[k] + wr / ntx;
-    tile_body_byte<R, GK, WRAPX, WRAPY, NW>(a, a.in, a.out, tx, ty, xch);
+    // per-XCD row-major runs and regions as the bit tiles (no bands, no tail: every item is a tile)
+    const TileItem it = tile_decode(a.d, blockIdx.x);
+    if (it.kind != kTileFull) return;
+    tile_body_byte<R, GK, WRAPX, WRAPY, NW>(a, a.in, a.out, it.tx, it.ty, xch);
 }
 
 // tflow_kernel: `passes` launches of the bit tiles (m generations each, both
@@ -1439,7 +1428,7 @@ __global__ __launch_bounds__(64 * NW, bit_wpe(NW, R)) void tflow_kernel(FArgs f)
 }
 
 // tflow_kernel again under a rule policy, for the 7-gate arm below (a twin for
-// the reason given at tstep_bit_body: tflow_kernel keeps its own text and so
+// the reason given at step_body: tflow_kernel keeps its own text and so
 // its code, the A/B arm and the instance tests/test_isa.py reads).  Queue,
 // dependency wait and hand-off are tflow_kernel's, line for line.
 template <int R, bool WRAPX, bool WRAPY, int FLOW, int NW, bool BAND, class RP>
@@ -2259,6 +2248,43 @@ static void set_bands(TArgs &a, const TileGeom &g) {
     }
 }
 
+// The 32-bit range tile_body_bit works in: pair columns up to W + 62 and
+// rows up to h + 17 T + NW R (a banded lane of the last item) below 2^31.
+static bool tile_body_fits32(const TArgs &a, int window_rows, int64_t nty) {
+    const int64_t lim = (int64_t)1 << 31, T = window_rows - 2 * (int64_t)a.m;
+    return a.W + 64 < lim && a.h + 66 * (int64_t)window_rows < lim && (nty + 17) * T + window_rows < lim &&
+           a.xoff + 8 * (a.W + 64) < 2 * lim;
+}
+// The item decode's constants of a bit launch (TArgs::d) from its regions,
+// bands, tail and XCD order; false: a count beyond the 32 bits the kernels
+// work in (no grid that fits in HBM comes near), the launch fails.
+static bool tile_args_seal(TArgs &a, int window_rows, int ghost, bool bit) {
+    life_tile_launch l = {};
+    l.nreg = a.nreg;
+    l.nband = bit ? a.nband : 0;  // (the byte tiles have no banded column)
+    l.m = ghost;                  // ghost rows at each end of a window: m (bit), the apron depth or 1 (byte)
+    l.window_rows = window_rows;
+    int64_t nty = 0;
+    for (int k = 0; k < a.nreg; k++) {
+        l.tx0[k] = a.tx0[k];
+        l.tx1[k] = a.tx1[k];
+        l.ty0[k] = a.ty0[k];
+        l.ty1[k] = a.ty1[k];
+        l.first[k] = a.first[k];
+        nty = std::max(nty, a.ty1[k]);
+    }
+    l.first[a.nreg] = a.first[a.nreg];
+    for (int i = 0; i < kMaxBands; i++) l.bgsh[i] = a.bgsh[i];
+    l.btx1 = a.btx1;
+    l.tail_first = a.tail_first;
+    l.tail_y = a.tail_y;
+    l.tail_yend = a.tail_yend;
+    l.tail_ntx = a.tail_ntx;
+    l.tail_tx0 = a.tail_tx0;
+    l.xcd_n = a.xcd_n;
+    return (!bit || tile_body_fits32(a, window_rows, nty)) && tile_decode_fill(l, &a.d);
+}
+
 hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out, const TileRegion *r, int nreg,
                         int m, Wrap wrap, hipStream_t s, double *valu_lane_ops, hipEvent_t ev0, hipEvent_t ev1,
                         Extend ext, int64_t concurrent, const RuleWords *rule, unsigned long long *pop, bool rule7) {
@@ -2331,6 +2357,7 @@ hipError_t launch_tstep(const life_layout &Lin, const uint8_t *in, uint8_t *out,
     }
     const bool split = a.tail_ntx > 0;
     a.xcd_n = (bit ? xcd_order_enabled() : xcd_order_byte_enabled()) ? (split ? a.tail_first : items) : 0;
+    if (!tile_args_seal(a, tile_waves(bit) * temporal_rows(bit), tile_ghost(L, m), bit)) return hipErrorInvalidValue;
     if (valu_lane_ops) {
         const double lane = 64.0 * tstep_valu_per_tile_lane(m, !bit, rule != nullptr, pop != nullptr);
         *valu_lane_ops = (double)(split ? a.tail_first : items) * lane;
@@ -2421,10 +2448,12 @@ hipError_t launch_tskip(const life_layout &L, const uint8_t *in, uint8_t *out, i
     a.btx1 = -1;  // plain tiles: no banded column, no tail split, dispatch order
     k.ntx = act_cols(a.W);
     k.nty = (L.h + T - 1) / T;
+    k.ntx_mul = tile_recip((uint32_t)k.ntx);
     k.cls = cls;
     k.act = dst_map;
     const int64_t tiles = k.ntx * k.nty;
-    if (tiles > 0x7fffffff) return hipErrorInvalidValue;
+    if (tiles > 0x7fffffff || !tile_body_fits32(a, tile_waves(true) * temporal_rows(true), k.nty))
+        return hipErrorInvalidValue;
     PlanArgs p{src_map, dst_map, cls, cnt, a.W, a.h, T, k.ntx, k.nty, m};
     act_plan_kernel<<<(unsigned)((tiles + 255) / 256), 256, 0, s>>>(p);
     hipError_t e = hipGetLastError();
@@ -2556,6 +2585,7 @@ hipError_t launch_tflow(const life_layout &L, const uint8_t *in, uint8_t *out, i
     f.items = passes * f.per_pass;
     f.head = head;
     f.done = done;
+    if (!tile_body_fits32(f.t, tile_waves(true) * temporal_rows(true), f.nty)) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(head, 0, sizeof(unsigned int), s);  // the error word is the caller's
     if (e == hipSuccess) e = hipMemsetAsync(done, 0, sizeof(unsigned int) * (size_t)(g.ntx * g.nty), s);
     if (e != hipSuccess) return e;

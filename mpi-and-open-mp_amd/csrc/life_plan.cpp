@@ -19,6 +19,7 @@
 #include "life_env.h"
 #include "life_host.h"
 #include "life_mi355x.h"
+#include "life_tile_decode.h"
 
 namespace {
 constexpr int64_t kXoff = 128;  // owned x = 0 starts 128 B into a padded row
@@ -538,6 +539,24 @@ int life_batch_query_plan(int64_t nx, int64_t ny, int *tier, int *words, int *la
     if (rows) *rows = group ? p.rows : 0;
     if (strips) *strips = group ? p.strips : 0;
     if (threads) *threads = 64 * p.waves_per_group;
+    return LIFE_OK;
+}
+
+int life_tile_decode_query(const life_tile_launch *launch, const int64_t *wg, int64_t n, life_tile_item *out) {
+    life::TileDec d;
+    const char *why = "null argument";
+    if (!launch || n < 0 || (n > 0 && (!wg || !out)) || !life::tile_decode_fill(*launch, &d, &why)) {
+        if (life::rt::set_err) life::rt::set_err("tile launch description: %s", why);
+        return LIFE_EINVAL;
+    }
+    for (int64_t i = 0; i < n; i++) {
+        if (wg[i] < 0 || wg[i] > 0x7FFFFFFFll) {  // a launch holds fewer than 2^31 workgroups
+            if (life::rt::set_err) life::rt::set_err("workgroup id %lld outside [0, 2^31)", (long long)wg[i]);
+            return LIFE_EINVAL;
+        }
+        const life::TileItem t = life::tile_decode(d, (uint32_t)wg[i]);
+        out[i] = life_tile_item{t.kind, t.region, t.tx, t.ty, t.ty0, t.rows, (int64_t)t.bi};
+    }
     return LIFE_OK;
 }
 

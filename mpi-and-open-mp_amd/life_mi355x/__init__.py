@@ -89,6 +89,7 @@ ABI_SYMBOLS = (
     "life_rule_parse_gen", "life_rule_format_gen", "life_batch_set_rule_gen", "life_batch_get_rule_gen",
     "life_batch_set_rules_gen", "life_batch_get_rules_gen", "life_batch_upload_states", "life_batch_gather_states",
     "life_batch_census_gen", "life_batch_query_plan", "life_batch_population", "life_batch_onsets",
+    "life_tile_decode_query",
 )
 GEN_MAX_STATES = 16  # LIFE_GEN_MAX_STATES
 BATCH_TIER_WAVE, BATCH_TIER_GROUP = 1, 2  # LIFE_BATCH_TIER_*

@@ -48,9 +48,18 @@ if flow:
     busy = [int(np.nansum((st[:, :, 1] <= x) & (st[:, :, 2] > x))) for x in ts]
     print("items computing over time (first 4 per workgroup only):", busy)
     sys.exit(0)
+phases = kernel == "bit" and bool((t[:, 3:6] > 0).all(axis=1).any())
+if phases:
+    # per-launch bit tiles: thread 64 stamps window loaded / generations done / stores issued (tile_body_bit)
+    ph = t[(t[:, 3:6] > 0).all(axis=1)].astype(np.int64)
+    head, body, tail = (ph[:, 3] - ph[:, 0]) / 100.0, (ph[:, 4] - ph[:, 3]) / 100.0, (ph[:, 5] - ph[:, 4]) / 100.0
+    q = lambda v: " ".join(f"{np.percentile(v, p):.2f}" for p in (10, 50, 90))  # noqa: E731
+    print(f"tile phases of {len(ph)} workgroups (pct 10/50/90, us): head (start -> window loaded) {q(head)} | "
+          f"generations {q(body)} | tail (-> stores issued) {q(tail)} | whole {q(head + body + tail)}")
 t0 = int(t[:, 0].min())
 start = (t[:, 0].astype(np.int64) - t0) / 100.0  # us
-tiles = np.where(t[:, 2:] > 0, (t[:, 2:].astype(np.int64) - t0) / 100.0, np.nan)  # end of each tile
+ends = t[:, 2:3] if phases else t[:, 2:]  # (with phase stamps: slot 2 is the end, slots 3-5 the phases above)
+tiles = np.where(ends > 0, (ends.astype(np.int64) - t0) / 100.0, np.nan)  # end of each tile
 end = np.nanmax(tiles, axis=1)
 hw = t[:, 1] & 0xFFFFFFFF
 xcc = (t[:, 1] >> 32) & 0xF
